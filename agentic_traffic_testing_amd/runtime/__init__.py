@@ -15,10 +15,20 @@ class StaleNativeBuild(ImportError):
     pass
 
 
+def _binary_embeds(path, digest: str) -> bool:
+    try:
+        return digest.encode() in path.read_bytes()
+    except OSError:
+        return False
+
+
 def _load():
     from ..ops import build
 
-    if os.environ.get("ATTA_NO_BUILD", "0") != "1":
+    # a binary that embeds the current source hash is used as is (checked on the file bytes):
+    # no build lock is taken, so a tree built by another user need not be writable
+    if os.environ.get("ATTA_NO_BUILD", "0") != "1" and not _binary_embeds(
+            build.runtime_so_path(), build.runtime_source_hash()):
         build.build_runtime()  # no-op when the stamp matches the sources
     mod = importlib.import_module("._atta_runtime", __name__)
     want = build.runtime_source_hash()

@@ -24,6 +24,12 @@ llama-3-70b`` for BASELINE configs 4/5) and prompts are synthetic (no network / 
 checkpoints), which ``data`` states.  ``--device cpu`` runs the same protocol on the CPU
 (gloo, tiny models) for the CPU test tier.
 
+A plain run (``--gpus 1 --steps N --warmup W``) sets up, warms up, times the N episodes and
+prints the result line; ``ms_per_step`` is the wall time of one timed episode.  ``--full``
+adds the measurements the headline does not need (one untimed uncached episode after the
+timed region).  ``--dump-outputs DIR`` writes the last timed episode's generated token ids
+and prompt lengths as ``DIR/<name>.npy`` for output-for-output comparison of two builds.
+
 Prints ONE JSON line on rank 0.
 """
 from __future__ import annotations
@@ -98,8 +104,15 @@ def _window_marker(a):
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--steps", type=int, default=3, help="timed episodes (>= 1)")
     ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the untimed "
+                         "uncached episode after the timed region (p50_ttft_uncached_s, "
+                         "ttft_by_phase_uncached)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed episode returned "
+                         "to its caller as DIR/<name>.npy (float32; --via engine only)")
     ap.add_argument("--model", default="meta-llama/Llama-3.1-8B-Instruct")
     ap.add_argument("--max-tokens", type=int, default=512)
     ap.add_argument("--fanout", type=int, default=5)
@@ -162,11 +175,26 @@ def self_launch(a) -> int:
     return subprocess.call(cmd, env=env)
 
 
+def _no_build_in_readonly_tree():
+    """The benchmark may run as another user than the one who built the tree.  Where the
+    package directory is not writable, the loaders are told not to build (ATTA_NO_BUILD=1):
+    they load the built libraries as they are and refuse stale ones, instead of failing on
+    the build lock file."""
+    ops_dir = os.path.join(ROOT, "agentic_traffic_testing_amd", "ops")
+    if "ATTA_NO_BUILD" not in os.environ and not os.access(ops_dir, os.W_OK):
+        os.environ["ATTA_NO_BUILD"] = "1"
+
+
 def main(argv=None):
     a = parse_args(argv)
+    _no_build_in_readonly_tree()
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if a.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if a.steps < 1:
+        raise SystemExit("--steps must be >= 1")
+    if a.dump_outputs and a.via == "http":
+        raise SystemExit("--dump-outputs needs --via engine")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return self_launch(a)
     if world != a.gpus:
@@ -200,6 +228,44 @@ def _sync(a):
         torch.cuda.synchronize()
 
 
+def record_outputs(eng) -> dict:
+    """--dump-outputs: keep every finished RequestOutput that ``eng.step()`` hands to its
+    caller, by request id (the workload names them ``ep<episode>-<request>``)."""
+    finished = {}
+    step = eng.step
+
+    def recording_step():
+        outs = step()
+        for o in outs:
+            if o.finished:
+                finished[o.request_id] = o
+        return outs
+
+    eng.step = recording_step
+    return finished
+
+
+def dump_outputs(dirname: str, finished: dict, episode: int) -> None:
+    """--dump-outputs: the arrays the caller of the timed path received in episode ``episode``
+    (the last timed one), one row per request in submission order (planning, the fan-out
+    burst, final synthesis).  ``token_ids`` holds the generated ids (exact in float32: the
+    vocabulary is < 2**24; rows shorter than the longest are padded with -1),
+    ``prompt_tokens`` the prompt lengths.  Weights, prompts and request seeds are seeded, so
+    two runs with the same arguments feed the engine the same inputs."""
+    import numpy as np
+
+    pre = f"ep{episode}-"
+    outs = [finished[r] for r in sorted((r for r in finished if r.startswith(pre)),
+                                        key=lambda r: int(r[len(pre):]))]
+    toks = np.full((len(outs), max(len(o.token_ids) for o in outs)), -1.0, dtype=np.float32)
+    for i, o in enumerate(outs):
+        toks[i, :len(o.token_ids)] = o.token_ids
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "token_ids.npy"), toks)
+    np.save(os.path.join(dirname, "prompt_tokens.npy"),
+            np.asarray([o.prompt_tokens for o in outs], dtype=np.float32))
+
+
 def main_dp(a, world: int):
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -226,6 +292,7 @@ def main_dp(a, world: int):
     eng.runner.capture_all(all_parts=True)
     init_s = time.perf_counter() - t0
     wl = FanoutWorkload(eng, fanout=a.fanout, max_tokens=a.max_tokens, seed=rank)
+    finished = record_outputs(eng) if a.dump_outputs and rank == 0 else None
 
     def log(*x):
         if a.verbose and rank == 0:
@@ -249,12 +316,14 @@ def main_dp(a, world: int):
         dist.barrier()
     elapsed = time.perf_counter() - t_start
     _window_marker(a)
-    # One untimed COLD episode after the timed region: prefix cache dropped first, so every
-    # prompt row is prefilled.  The timed episodes cycle 4 tasks and hit the prefix cache from
-    # episode 5 on (only the "(episode N)" suffix is new), so their TTFT is the cached regime;
-    # this line reports the uncached one beside it.  Not part of value / ms_per_step.
+    if finished is not None:
+        dump_outputs(a.dump_outputs, finished, wl.episode_idx - 1)
+    # --full: one untimed COLD episode after the timed region: prefix cache dropped first, so
+    # every prompt row is prefilled.  The timed episodes cycle 4 tasks and hit the prefix cache
+    # from episode 5 on (only the "(episode N)" suffix is new), so their TTFT is the cached
+    # regime; this line reports the uncached one beside it.  Not part of value / ms_per_step.
     cold = None
-    if a.steps > 0:
+    if a.full:
         eng.runner.reset_state()
         cold = wl.run_episode()
 
@@ -322,13 +391,14 @@ def main_dp(a, world: int):
             "p95_ttft_s": round(p95, 4) if p95 is not None else None,
             "p50_latency_s": round(statistics.median(lat), 3) if lat else None,
             "ttft_by_phase": ttft_phases,
-            "p50_ttft_uncached_s": (round(statistics.median(cold_ttfts), 4)
-                                    if cold_ttfts else None),
-            "ttft_by_phase_uncached": cold_phases,
             "requests_per_step_per_gpu": 2 + a.fanout,
             "completion_tokens": int(tokens),
             "init_s": round(init_s, 1),
         }
+        if a.full:
+            out["p50_ttft_uncached_s"] = (round(statistics.median(cold_ttfts), 4)
+                                          if cold_ttfts else None)
+            out["ttft_by_phase_uncached"] = cold_phases
         print(json.dumps(out), flush=True)
     if dist:
         dist.barrier()
@@ -424,6 +494,7 @@ def main_tp(a):
     init_s = time.perf_counter() - t0
     try:
         wl = FanoutWorkload(eng, fanout=a.fanout, max_tokens=a.max_tokens, seed=0)
+        finished = record_outputs(eng) if a.dump_outputs else None
         for _ in range(a.warmup):
             wl.run_episode()
         eng.runner.barrier()
@@ -431,6 +502,8 @@ def main_tp(a):
         results = [wl.run_episode() for _ in range(a.steps)]
         eng.runner.barrier()
         elapsed = time.perf_counter() - t_start
+        if finished is not None:
+            dump_outputs(a.dump_outputs, finished, wl.episode_idx - 1)
     except BaseException:
         eng.shutdown()
         raise

@@ -8,7 +8,8 @@
 # Recipes (profiles they produced in round 4):
 #   final        tests + smoke + 5-step bench + profbench + 3092-token prefill profile
 #                (r4_final_gpu_tier.log, r4_final_profbench_summary.txt, r4_prof_prefill3k_after_summary.txt)
-#   driverlike   bench.py --gpus 1 --steps 20 --warmup 5, the driver's invocation (r4_driverlike_bench.log)
+#   driverlike   bench.py --gpus 1 --steps 20 --warmup 5 --full: the headline invocation plus the
+#                uncached episode the result tables cite (r4_driverlike_bench.log); log in $LOGS (logs/)
 #   refresh      HTTP fan-out, 8B fp8, 70B fp8 TP=1 benches (r4_final_secondary.log)
 #   tp8          TP=8 rehearsal (8 ranks on one GPU) with graph node dumps, push on / off, and the
 #                AgentVerse HTTP runs on 8B and 70B fp8 (r4_tp8_*, r4_http_agentverse_*)
@@ -38,8 +39,9 @@ recipe() {
       TAG=r4final STAGES="tests smoke bench profbench" STEPS=${STEPS:-5} TEST_TIMEOUT=1000 bash $S &&
       TAG=r4finalpf3k STAGES=profpf TOKENS=3092 SEQS=1 bash $S ;;
     driverlike)
-      timeout -k 10 900 python bench.py --gpus 1 --steps 20 --warmup 5 > gpurun_out/r4_driverlike_bench.log 2>&1 &&
-      tail -1 gpurun_out/r4_driverlike_bench.log ;;
+      mkdir -p "${LOGS:=logs}" &&
+      timeout -k 10 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > "$LOGS/driverlike_bench.log" 2>&1 &&
+      tail -1 "$LOGS/driverlike_bench.log" ;;
     refresh)
       TAG=r4fin STAGES=http STEPS=3 bash $S &&
       TAG=r4fin_fp8 STAGES=bench STEPS=2 BENCH_ARGS="--quantization fp8" bash $S &&

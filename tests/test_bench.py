@@ -49,6 +49,38 @@ def test_bench_gpus1_cpu_matches_contract():
     for k in ("metric", "value", "unit", "steps", "warmup", "ms_per_step", "vs_baseline",
               "dtype", "data", "config"):
         assert k in o
+    # a plain run measures the headline only: the uncached episode is behind --full
+    assert "p50_ttft_uncached_s" not in o and "ttft_by_phase_uncached" not in o
+
+
+def test_bench_full_and_dump_outputs_cpu(tmp_path):
+    """--full adds the uncached episode; --dump-outputs writes the last timed episode's
+    outputs, identical from run to run (seeded weights, prompts and request seeds), and
+    --steps sets the number of timed episodes."""
+    import numpy as np
+
+    args = ["--gpus", "1", *SMALL[:4], "--steps", "2", *SMALL[6:]]
+    r, out = _run([*args, "--full", "--dump-outputs", str(tmp_path / "a")])
+    assert r.returncode == 0, r.stderr[-3000:]
+    o = out[0]
+    assert o["steps"] == 2 and o["completion_tokens"] == 2 * 7 * 4
+    assert o["p50_ttft_uncached_s"] > 0 and set(o["ttft_by_phase_uncached"]) == set(
+        o["ttft_by_phase"])
+    r, out = _run([*args, "--dump-outputs", str(tmp_path / "b")])
+    assert r.returncode == 0, r.stderr[-3000:]
+    for d in ("a", "b"):
+        assert sorted(p.name for p in (tmp_path / d).iterdir()) == ["prompt_tokens.npy",
+                                                                    "token_ids.npy"]
+    ta, tb = (np.load(tmp_path / d / "token_ids.npy") for d in ("a", "b"))
+    assert ta.dtype == np.float32 and ta.shape == (7, 4) and (ta >= 0).all()
+    assert np.array_equal(ta, tb)
+    pa, pb = (np.load(tmp_path / d / "prompt_tokens.npy") for d in ("a", "b"))
+    assert pa.dtype == np.float32 and pa.shape == (7,) and np.array_equal(pa, pb)
+
+
+def test_bench_steps_must_be_positive():
+    r, _ = _run(["--gpus", "1", *SMALL[:4], "--steps", "0"])
+    assert r.returncode != 0 and "--steps must be >= 1" in r.stderr
 
 
 def test_bench_too_many_gpus_errors():

@@ -85,6 +85,22 @@ def test_current_library_is_used_without_object_files(tmp_path, monkeypatch):
     assert calls == []
 
 
+def test_current_runtime_is_used_without_build_lock(monkeypatch):
+    """A runtime binary that embeds the current source hash is imported as is: no build, no
+    lock file - a tree built by another user need not be writable - and a stale one is
+    detected from its bytes."""
+    from agentic_traffic_testing_amd import runtime
+
+    so = build.build_runtime()
+    assert runtime._binary_embeds(so, build.runtime_source_hash())
+    assert not runtime._binary_embeds(so, "0" * 32)
+    calls = []
+    monkeypatch.setattr(build, "build_runtime", lambda *a, **k: calls.append(1))
+    monkeypatch.setattr(build, "_build_lock", lambda: calls.append(2))
+    assert runtime._load().BUILD_HASH == build.runtime_source_hash()
+    assert calls == []
+
+
 def test_build_lock_serialises_processes(tmp_path):
     """Two processes holding the build lock never overlap."""
     import subprocess
