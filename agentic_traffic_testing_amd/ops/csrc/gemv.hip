@@ -6,9 +6,14 @@
 // the batch) is 1..16, so the layer GEMMs are pure HBM streams (guide: "GEMV / M <= 16
 // decode weights: load straight to VGPRs, deep unroll, late vmcnt").  Structure:
 //   * a workgroup owns one 16-column output tile; WAVES waves split K; each wave streams
-//     its K slice of the tile's 16 weight rows with 16-byte loads, two register stages of
-//     UNROLL loads each (software pipelined: the next stage is in flight while the current
-//     one feeds the MFMAs);
+//     its K slice of the tile's 16 weight rows with 16-byte loads through two register
+//     stages.  One row tile of 16-bit weights (every decode step): a stage holds UNROLL
+//     weight loads AND the UNROLL x fragments they meet, issued together one stage ahead of
+//     use with no load under a branch, so the MFMAs of stage s wait with vmcnt(loads of
+//     stage s + 1) and the next stage stays in flight across them (skinny.h, PIPE).  Two
+//     row tiles and fp8 weights keep the older order - next stage's weights, then this
+//     stage's x under an exec mask, then vmcnt(0) - which drains the queue every stage but
+//     needs fewer registers (profiles/r7_gemv_pipeline_isa.txt);
 //   * the 16 rows x 32 k chunk is the B operand of mfma_f32_16x16x32_bf16 (lane l: weight
 //     row rows(tile, l&15), k = 8(l>>4)..+8); x rows are the A operand (lane l: row l&15,
 //     L1/L2 resident; rows >= M are zeros);
@@ -108,7 +113,10 @@ static void launch_epi(int dtype, int mt, int waves, dim3 grid, hipStream_t st,
   // (waves, unroll) picked from cold-cache on-device sweeps (profiles/r1_microbench_*):
   // row-major 16-bit weights: 8 x 2 for the small projections, 16 x 2 for the large ones;
   // pre-shuffled 16-bit weights: 8 waves stream best with 4-deep stages (o, down), 16 x 2
-  // (gate_up, lm_head), 4 x 4 (qkv).  fp8 doubles the depth inside launch_t.
+  // (gate_up, lm_head), 4 x 4 (qkv).  fp8 doubles the depth inside launch_t.  Re-swept on the
+  // pipelined loop (waves {4, 8, 16} x unroll {2, 4, 8}, profiles/r7_gemv_pipeline_ab.txt):
+  // 8-deep stages never win, the rest lie within 5 % of these picks cold and no other wave
+  // count won in situ, so the table stands.
   const bool ps16 = p.ps && p.wscale == nullptr;
   if (waves == 16) {
     if (mt == 1) launch_t<16, 2, 1, EPI>(dtype, grid, st, p);
@@ -492,8 +500,9 @@ int atta_skinny_variant(void* y, const void* x, const void* w, int M, int N, int
   p.ksplit = 1;
   if (M < 1 || M > 16 || N % 16) return -1;
   dim3 grid(N / 16);
-  static const int waves_of[14] = {8, 8, 4, 4, 8, 16, 8, 16, 8, 16, 8, 16, 4, 4};
-  if (variant < 0 || variant > 13 || K % (32 * waves_of[variant])) return -1;
+  static const int waves_of[23] = {8, 8, 4, 4, 8, 16, 8, 16, 8, 16, 8, 16, 4, 4,
+                                   4, 4, 4, 8, 8, 8, 16, 16, 16};
+  if (variant < 0 || variant > 22 || K % (32 * waves_of[variant])) return -1;
   switch (variant) {
     case 0: skinny_kernel<__bf16, 8, 4, 1, EPI_PLAIN, true><<<grid, 512, 0, stream>>>(p); break;
     case 1: skinny_kernel<__bf16, 8, 8, 1, EPI_PLAIN, false><<<grid, 512, 0, stream>>>(p); break;
@@ -510,6 +519,16 @@ int atta_skinny_variant(void* y, const void* x, const void* w, int M, int N, int
     case 11: skinny_kernel<__bf16, 16, 4, 1, EPI_PLAIN, false, true><<<grid, 1024, 0, stream>>>(p); break;
     case 12: skinny_kernel<__bf16, 4, 4, 1, EPI_PLAIN, false, true><<<grid, 256, 0, stream>>>(p); break;
     case 13: skinny_kernel<__bf16, 4, 8, 1, EPI_PLAIN, false, true><<<grid, 256, 0, stream>>>(p); break;
+    // 14-22: pre-shuffled + non-temporal (the production load policy), waves x unroll grid
+    case 14: skinny_kernel<__bf16, 4, 2, 1, EPI_PLAIN, true, true><<<grid, 256, 0, stream>>>(p); break;
+    case 15: skinny_kernel<__bf16, 4, 4, 1, EPI_PLAIN, true, true><<<grid, 256, 0, stream>>>(p); break;
+    case 16: skinny_kernel<__bf16, 4, 8, 1, EPI_PLAIN, true, true><<<grid, 256, 0, stream>>>(p); break;
+    case 17: skinny_kernel<__bf16, 8, 2, 1, EPI_PLAIN, true, true><<<grid, 512, 0, stream>>>(p); break;
+    case 18: skinny_kernel<__bf16, 8, 4, 1, EPI_PLAIN, true, true><<<grid, 512, 0, stream>>>(p); break;
+    case 19: skinny_kernel<__bf16, 8, 8, 1, EPI_PLAIN, true, true><<<grid, 512, 0, stream>>>(p); break;
+    case 20: skinny_kernel<__bf16, 16, 2, 1, EPI_PLAIN, true, true><<<grid, 1024, 0, stream>>>(p); break;
+    case 21: skinny_kernel<__bf16, 16, 4, 1, EPI_PLAIN, true, true><<<grid, 1024, 0, stream>>>(p); break;
+    case 22: skinny_kernel<__bf16, 16, 8, 1, EPI_PLAIN, true, true><<<grid, 1024, 0, stream>>>(p); break;
     default: return -1;
   }
   return static_cast<int>(hipGetLastError());

@@ -223,6 +223,11 @@ __device__ __forceinline__ void tile_epilogue(const SkinnyParams& p, const int t
   }
 }
 
+// Main-loop load order of skinny_body: true = two-stage register pipeline ({w, x} of stage
+// s + 1 in flight across the MFMAs of stage s), false = the drained order (docs/kernels.md,
+// "Skinny decode GEMV").  16-bit weights with one row tile (every decode step) pipeline.
+constexpr bool skinny_pipelined(int mt, bool w8) { return mt == 1 && !w8; }
+
 // Weight layouts.  Row-major [N][K]: a wave's 16-byte-per-lane load touches 16 rows x 64 B
 // (16 DRAM pages per instruction).  Pre-shuffled (PS): for every 16-row tile (rows already
 // permuted by tile_row<EPI>) and every 32-wide K step, the 16 x 32 block is stored as the
@@ -235,7 +240,7 @@ __device__ __forceinline__ void tile_epilogue(const SkinnyParams& p, const int t
 // consecutive 32-wide K steps - converted to 16-bit MFMA operands in registers; the
 // per-row scale multiplies the reduced accumulator.  Halves the weight stream.
 template <typename T, int WAVES, int UNROLL, int MT, int EPI, bool NTL = false, bool PS = false,
-          bool W8 = false>
+          bool W8 = false, bool PIPE = skinny_pipelined(MT, W8)>
 __device__ __forceinline__ void skinny_body(const SkinnyParams& p, const int tile, const int ks,
                                             const int ksplit) {
   static_assert(!W8 || (UNROLL % 2 == 0), "fp8 weights load K-step pairs");
@@ -319,7 +324,64 @@ __device__ __forceinline__ void skinny_body(const SkinnyParams& p, const int til
       }
     }
   };
-  if (nsteps > 0) {
+  if constexpr (PIPE) {
+    // Two-stage register pipeline.  A stage is its weight registers AND its x fragments,
+    // issued together one stage ahead of use: s_waitcnt vmcnt counts loads in issue order,
+    // so a stage's MFMAs can wait for "all but the next stage's loads" only if nothing the
+    // current stage needs is issued after them.  The x loads are unconditional (xp[t] is
+    // clamped to row 0 for rows >= M, the fragment is zeroed by select) and the last one
+    // or two stages are peeled, so the loop body has no load under a branch or exec mask
+    // (a join would force vmcnt(0) again).  load_stage(k) is only called with
+    // k + STEP <= kw; MFMA / sq8 order is that of the drained loop below (bit-identical).
+    struct Stage {
+      Raw w[NRAW];
+      frag8 x[MT][UNROLL];
+    };
+    auto load_stage = [&](Stage& st, int k) {
+      load_w(st.w, k);
+#pragma unroll
+      for (int t = 0; t < MT; ++t)
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u)
+          st.x[t][u] = *reinterpret_cast<const frag8*>(xp[t] + k + 32 * u);
+    };
+    auto compute_stage = [&](const Stage& st) {
+      frag8 wf[UNROLL];
+#pragma unroll
+      for (int u = 0; u < UNROLL; ++u) wf[u] = wfrag(st.w, u);
+#pragma unroll
+      for (int t = 0; t < MT; ++t) {
+#pragma unroll
+        for (int u = 0; u < UNROLL; ++u) {
+          const frag8 xf = xv[t] ? st.x[t][u] : frag8{};
+          acc[t] = MF::mma(xf, wf[u], acc[t]);
+          if (norm) ss[t] = MF::sq8(xf, ss[t]);
+        }
+      }
+    };
+    if (nsteps > 0) {
+      Stage sa, sb;
+      load_stage(sa, 0);
+      int s = 0;
+      for (; s + 2 < nsteps; s += 2) {  // steady state: stages s + 1 and s + 2 both exist
+        load_stage(sb, (s + 1) * STEP);
+        compute_stage(sa);
+        load_stage(sa, (s + 2) * STEP);
+        compute_stage(sb);
+      }
+      if (s + 1 < nsteps) {  // peeled tail: sa holds stage s; one or two stages are left
+        load_stage(sb, (s + 1) * STEP);
+        compute_stage(sa);
+        compute_stage(sb);
+      } else {
+        compute_stage(sa);
+      }
+    }
+  } else if (nsteps > 0) {
+    // Drained order (MT == 2, fp8 weights): compute() issues the stage's x loads after
+    // load_w() has issued the next stage's weights, so the wait for x is vmcnt(0) and each
+    // stage drains the wave's load queue; kept where the pipelined order costs registers
+    // (spills / an occupancy class).
     Raw wa[NRAW], wb[NRAW];
     load_w(wa, 0);
     int s = 0;

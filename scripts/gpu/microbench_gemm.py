@@ -21,8 +21,12 @@ SHAPES = [("qkv", 6144, 4096), ("o", 4096, 4096), ("gate_up", 28672, 4096),
           ("down", 4096, 14336), ("lm_head", 128256, 4096)]
 VARIANTS = {0: "w8u4-nt", 1: "w8u8", 2: "w4u4", 3: "w4u8", 4: "w8u4", 5: "w16u4",
             6: "w8u2", 7: "w16u2", 8: "w8u2-ps", 9: "w16u2-ps", 10: "w8u4-ps",
-            11: "w16u4-ps", 12: "w4u4-ps", 13: "w4u8-ps"}
-PRESHUFFLED = {8, 9, 10, 11, 12, 13}
+            11: "w16u4-ps", 12: "w4u4-ps", 13: "w4u8-ps",
+            # pre-shuffled + non-temporal: the production load policy, waves x unroll grid
+            14: "w4u2-ps-nt", 15: "w4u4-ps-nt", 16: "w4u8-ps-nt", 17: "w8u2-ps-nt",
+            18: "w8u4-ps-nt", 19: "w8u8-ps-nt", 20: "w16u2-ps-nt", 21: "w16u4-ps-nt",
+            22: "w16u8-ps-nt"}
+PRESHUFFLED = set(range(8, 23))
 SWEEP = os.environ.get("MB_VARIANTS")  # e.g. "6,7,8,9,10,11,12,13"
 
 
