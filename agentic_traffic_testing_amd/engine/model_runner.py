@@ -412,7 +412,7 @@ class ModelRunner:
         m = self.model
         T = v["input_ids"].shape[0]
         if (self.fused_decode and md.num_tiles == 0
-                and md.num_decode == T and m.decode_fusable(T)):
+                and md.num_decode == T and m.decode_step_fusable(T)):
             ws = self._ws_for(T)
             # grid over this step's partition bucket only (num_parts covers every row, in
             # the partition size of this batch size: parts_bucket)
@@ -428,8 +428,7 @@ class ModelRunner:
                          prev_tokens=self.ws["tokens"] if decode_only else None,
                          feed_prev=v["feed_prev"] if decode_only else None,
                          rows=v["logits_idx"])
-        if not special and m.decode_fusable(last.shape[0]) and \
-                last.shape[0] <= self.max_seqs and m.hidden_fusable():
+        if not special and m.sampler_fusable(last.shape[0]) and last.shape[0] <= self.max_seqs:
             # fused LM head + Gumbel-max sampler on the (already normalised) last rows
             return m.sample_rows(last, 0.0, v["temperature"], v["seeds"], v["steps"], self.ws)
         logits = m.compute_logits(last)
@@ -452,7 +451,7 @@ class ModelRunner:
         if c is None or c.size == 1 or not c.is_gloo:
             return True
         return (c.decode_capturable and not special and self.fused_decode
-                and self.model.decode_fusable(bucket))
+                and self.model.decode_step_fusable(bucket))
 
     def graph_bucket(self, batch: Batch) -> int:
         """Graph bucket a decode-only batch replays from (0: eager step)."""

@@ -118,6 +118,12 @@ class LlamaModel:
         self.cos_sin = ref.rope_cos_sin(cfg.head_dim, min(cfg.max_position_embeddings, 1 << 17),
                                         cfg.rope_theta, cfg.rope_scaling, device=self.device)
         self.g = self.n_heads // self.n_kv_heads
+        # every projection's K in whole wave steps of the weight-streaming kernels (16-bit
+        # GEMVs: K % 128 = 4 waves x 32; fp8: K % 256 = 4 waves x 64) - proj_fusable
+        step = 256 if self.quant == "fp8" else 128
+        self._proj_dims_ok = (self.device.type == "cuda" and cfg.hidden_size % step == 0
+                              and self.inter % step == 0
+                              and (self.n_heads * self.head_dim) % step == 0)
         if self.head_dim != 128 and self.device.type == "cuda":
             raise ValueError("HIP attention kernels require head_dim 128")
 
@@ -500,10 +506,9 @@ class LlamaModel:
         """{projection: True} for the projections of a T-row step that run the mid-M kernel
         (empty when the step cannot: TP, fp8, no pre-shuffled weights, rows past
         ops.MIDM_MAX_M)."""
-        if (T <= 128 or T > ops.fused_max_rows(True, False) or self.quant == "fp8"
-                or self.tp_size != 1 or not self.fused_decode or not self.small_prefill_fused
-                or not self.decode_fusable(min(T, 128)) or not self.layers
-                or self.layers[0].qkv_ps is None):
+        if (T <= ops.WIDE_ROWS or self.quant == "fp8" or self.tp_size != 1
+                or not self.fused_decode or not self.small_prefill_fused
+                or not self.proj_fusable(T)):
             return {}
         return {p: any(lo <= T <= hi for lo, hi in r) for p, r in self.MIDM_ROUTES.items()}
 
@@ -529,21 +534,21 @@ class LlamaModel:
 
     def _fp8_fused_max(self) -> int:
         if self.tp_size > 1:
-            return 128
-        return self.FP8_FUSED_MAX_ROWS.get(self.cfg.hidden_size, 128)
+            return ops.WIDE_ROWS
+        return self.FP8_FUSED_MAX_ROWS.get(self.cfg.hidden_size, ops.WIDE_ROWS)
 
     def _fp8_gate_up_max(self) -> int:
-        if self.tp_size > 1:
-            return 128  # the TP shards' library GEMMs are launch-bound: not measured past it
-        return self.FP8_GATE_UP_WIDE_MAX.get(self.cfg.hidden_size, 128)
+        if self.tp_size > 1:  # the TP shards' library GEMMs are launch-bound: not measured past it
+            return ops.WIDE_ROWS
+        return self.FP8_GATE_UP_WIDE_MAX.get(self.cfg.hidden_size, ops.WIDE_ROWS)
 
     def midm_fp8_ok(self, T: int) -> bool:
-        """Does an fp8 step of T > 128 rows run every projection on the mid-M W8 builds?"""
+        """Does an fp8 step past the wide kernel's rows run every projection on the mid-M W8
+        builds?"""
         lo, hi = self.MIDM_FP8_ROWS
-        return (self.quant == "fp8" and 128 < T and lo <= T <= hi
-                and T <= ops.fused_max_rows(True, True) and self.tp_size == 1
-                and self.fused_decode and self.small_prefill_fused
-                and self.device.type == "cuda" and self.decode_fusable(T))
+        return (self.quant == "fp8" and ops.WIDE_ROWS < T and lo <= T <= hi
+                and self.tp_size == 1 and self.fused_decode and self.small_prefill_fused
+                and self.proj_fusable(T))
 
     def small_prefill_ok(self, T: int) -> bool:
         """Does a (prefill or mixed) step of T rows run on the fused decode kernels - RMSNorm
@@ -556,32 +561,32 @@ class LlamaModel:
         if self.quant == "fp8":
             if T > self._fp8_fused_max() or not (self.layers and self.layers[0].qkv_ps is not None):
                 return False
-        return (self.small_prefill_fused and self.fused_decode and self.device.type == "cuda"
-                and T <= 128 and self.decode_fusable(T))
+        return (self.small_prefill_fused and self.fused_decode and T <= ops.WIDE_ROWS
+                and self.proj_fusable(T))
 
-    def decode_fusable(self, num_tokens: int) -> bool:
-        """Can a step of this many rows run the fused weight-streaming kernels?  <= 32 rows:
-        the 16-row-tile GEMVs (any layout); 33..128 rows: the wide small-M kernel over the
-        pre-shuffled 16-bit or fp8 weights (any TP degree: past the fused push's 32 rows the
-        row-parallel sums take the IPC / RCCL all-reduce); 129..ops.MIDM_MAX_M rows: the mid-M
-        kernel (16-bit weights, TP = 1)."""
-        # 16-bit GEMVs: K % 128 (4 waves x 32); fp8 GEMVs: K % 256 (4 waves x 64)
-        step = 256 if self.quant == "fp8" else 128
-        dims = (self.device.type == "cuda" and self.cfg.hidden_size % step == 0
-                and self.inter % step == 0 and (self.n_heads * self.head_dim) % step == 0)
-        if not dims or num_tokens < 1:
-            return False
-        if num_tokens <= ops.SKINNY_MAX_M:
-            return True
-        lim = ops.fused_max_rows(True, self.quant == "fp8")
-        if self.tp_size > 1:
-            lim = min(lim, 128)  # the mid-M routes are measured at TP = 1 shapes only
-        return (num_tokens <= lim and bool(self.layers) and self.layers[0].qkv_ps is not None
-                and self.lm_head_ps is not None)
+    def proj_fusable(self, T: int) -> bool:
+        """Can the layer projections of a T-row step run the hand-written weight-streaming
+        kernels (ops.fused_kernel: the 16-row-tile GEMVs on any layout, the wide small-M and
+        mid-M kernels over the pre-shuffled 16-bit or fp8 weights)?  Any TP degree up to the
+        wide kernel's rows (past the fused push's rows the row-parallel sums take the IPC /
+        RCCL all-reduce); the mid-M routes are measured at TP = 1 shapes only."""
+        ps = bool(self.layers) and self.layers[0].qkv_ps is not None
+        return (self._proj_dims_ok and (self.tp_size == 1 or T <= ops.WIDE_ROWS)
+                and ops.fused_kernel(T, ps, ps and self.quant == "fp8") is not None)
 
-    def hidden_fusable(self) -> bool:
-        """The LM-head GEMV streams K = hidden in 128-wide (16-bit) wave steps."""
-        return self.device.type == "cuda" and self.cfg.hidden_size % 128 == 0
+    def decode_step_fusable(self, B: int) -> bool:
+        """Can ``forward_decode`` run B sequences?  It runs every projection fused (gate_up
+        included, which loses to the library past the wide kernel's rows: MIDM_ROUTES) and
+        ends in the fused LM head + sampler."""
+        return (self.proj_fusable(B) and B <= min(ops.fused_max_rows(), ops.WIDE_ROWS)
+                and self.sampler_fusable(B))
+
+    def sampler_fusable(self, rows: int) -> bool:
+        """Can ``sample_rows`` take these rows?  The LM-head kernels with the sampler epilogue,
+        streaming K = hidden in 128-wide (16-bit) wave steps."""
+        lm_ps = self.lm_head_ps is not None
+        return (self.device.type == "cuda" and self.cfg.hidden_size % 128 == 0
+                and ops.fused_kernel(rows, lm_ps, False, "sample") is not None)
 
     def forward_decode(self, input_ids: torch.Tensor, md: AttnMeta, k_caches, v_caches, ws: dict,
                        temperature, seeds, steps, prev_tokens=None,
@@ -646,10 +651,11 @@ class LlamaModel:
                            proj=proj), residual)
 
     def sample_rows(self, x, eps, temperature, seeds, steps, ws) -> torch.Tensor:
-        """[final RMSNorm (eps > 0) +] LM head + sampler for <= 32 rows without materialising
-        logits; tokens land in ws["tokens"][:B] on every rank (an async look-ahead step embeds
-        them from there).  Used by the fused decode step and for the last-token rows of
-        prefill steps (their rows are already normalised: eps = 0)."""
+        """[final RMSNorm (eps > 0) +] LM head + sampler for ``sampler_fusable`` rows (<= 32 on
+        row-major weights, <= 128 pre-shuffled) without materialising logits; tokens land in
+        ws["tokens"][:B] on every rank (an async look-ahead step embeds them from there).  Used
+        by the fused decode step and for the last-token rows of prefill steps (their rows are
+        already normalised: eps = 0)."""
         B = x.shape[0]
         lm_ps = self.lm_head_ps is not None
         lm = self.lm_head_ps if lm_ps else self.lm_head

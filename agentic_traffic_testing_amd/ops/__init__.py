@@ -70,7 +70,7 @@ def load_native(build_if_missing: bool = True) -> bool:
         torch.ops.atta.set_splitk_half(SPLITK_HALF)
         torch.ops.atta.set_flash_split_blocks(FLASH_SPLIT_BLOCKS)
         if WIDE_MAX_M <= SKINNY_MAX_M:  # wide kernel off: no <= 32-row call may take it
-            torch.ops.atta.set_wide_min_rows(33, 33)
+            set_wide_min_rows(SKINNY_ROWS + 1, SKINNY_ROWS + 1)
     except Exception as e:  # pragma: no cover - depends on environment
         _load_error = f"{type(e).__name__}: {e}"
     return _loaded
@@ -382,18 +382,47 @@ WIDE_MAX_M = int(os.environ.get("ATTA_WIDE_MAX_M", "128"))
 # row-blocked BM x 128 tiles, ~256 workgroups, the same fused epilogues) - the uncached burst
 # and planning prefills.  Needs the wide kernel on up to 128 rows; 0 turns it off.
 MIDM_MAX_M = int(os.environ.get("ATTA_MIDM_MAX_M", "1024"))
+# the three above are routing policy; these are the rows the kernels themselves take
+# (csrc/skinny.h: kSkinnyMaxM, kWideMaxM, kMidmMaxM)
+SKINNY_ROWS, WIDE_ROWS, MIDM_ROWS = 32, 128, 8192
+# pre-shuffled 16-bit calls run the wide kernel from this many rows (gate_up + SiLU: the
+# second); set_wide_min_rows keeps the pair in step with the library's
+_wide_min_rows = [17, 12]
 
 
-def fused_max_rows(preshuffled: bool = True, fp8: bool = False) -> int:
-    """Most rows a call may have to run on the hand-written weight-streaming kernels (the
-    16-row-tile GEMVs, the wide small-M kernel, the mid-M kernel) for this weight format:
-    pre-shuffled 16-bit or fp8 weights (the W8 builds of the wide / mid-M kernels)."""
-    del fp8  # both kernels have fp8-weight builds
-    if not preshuffled or WIDE_MAX_M <= SKINNY_MAX_M:
-        return SKINNY_MAX_M
-    if WIDE_MAX_M >= 128 and MIDM_MAX_M > 128:
-        return MIDM_MAX_M
-    return min(WIDE_MAX_M, 128)
+def _policy_tops() -> tuple[int, int, int]:
+    """Most rows the policy limits let the 16-row-tile GEMV, the wide and the mid-M kernel
+    take (0: kernel off).  The mid-M kernel needs the wide kernel on up to its 128 rows."""
+    wide_top = min(WIDE_MAX_M, WIDE_ROWS) if WIDE_MAX_M > SKINNY_MAX_M else 0
+    midm_top = min(MIDM_MAX_M, MIDM_ROWS) if wide_top == WIDE_ROWS else 0
+    return min(SKINNY_MAX_M, SKINNY_ROWS), wide_top, (midm_top if midm_top > WIDE_ROWS else 0)
+
+
+def fused_kernel(m: int, preshuffled: bool, fp8: bool = False, epi: str = "plain") -> str | None:
+    """Which hand-written weight-streaming kernel runs ``m`` rows over this weight layout with
+    this epilogue ("plain" | "resadd" | "qkv" | "silu" | "sample" | "push"): "skinny" (the
+    16-row-tile GEMV), "wide", "midm", or None (no kernel: the native call would fail).  The
+    routing table of csrc/gemv.hip ``route()`` (written out there and in docs/kernels.md)
+    under the policy limits above.  Pure: no native call, usable without a GPU."""
+    skinny_top, wide_top, midm_top = _policy_tops()
+    if m < 1:
+        return None
+    if not (preshuffled or fp8) or epi == "push" or not wide_top:
+        return "skinny" if m <= skinny_top else None
+    if m <= SKINNY_ROWS and (fp8 or m < _wide_min_rows[1 if epi == "silu" else 0]):
+        return "skinny"
+    if epi == "sample" and fp8:
+        return None
+    if m <= wide_top:
+        return "wide"
+    return "midm" if epi != "sample" and WIDE_ROWS < m <= midm_top else None
+
+
+def fused_max_rows(preshuffled: bool = True) -> int:
+    """Most rows a projection (any epilogue but the sampler's) may have to run on the
+    hand-written weight-streaming kernels: row-major weights, or pre-shuffled 16-bit / fp8."""
+    tops = _policy_tops()
+    return max(tops) if preshuffled else tops[0]
 
 
 SKINNY_WAVES = int(os.environ.get("ATTA_SKINNY_WAVES", "8"))
@@ -495,13 +524,12 @@ def _ksplit(proj: str, x: torch.Tensor, ksplit: int | None, tiles: int) -> int:
 
 def skinny_ok(x: torch.Tensor, w: torch.Tensor, preshuffled: bool = False,
               fp8: bool = False) -> bool:
-    """Does ``x @ w.T`` run on the hand-written MFMA kernels?  <= SKINNY_MAX_M rows on any
-    16-bit / fp8 layout (gemv.hip); up to ``fused_max_rows()`` rows on pre-shuffled 16-bit
-    weights (wide.hip to 128 rows, midm.hip beyond)."""
+    """Does ``x @ w.T`` run on the hand-written MFMA kernels?  Shapes they take, and a row
+    count ``fused_kernel`` names a kernel for."""
     m, k = x.shape
-    lim = fused_max_rows(preshuffled, fp8)
-    return (x.is_cuda and 1 <= m <= lim and w.shape[0] % 16 == 0
-            and k % 128 == 0 and x.stride(1) == 1 and w.is_contiguous())
+    return (x.is_cuda and fused_kernel(m, preshuffled, fp8) is not None
+            and w.shape[0] % 16 == 0 and k % 128 == 0 and x.stride(1) == 1
+            and w.is_contiguous())
 
 
 def set_wide_plan(waves: int = 0, ksplit: int = 0) -> None:
@@ -536,18 +564,17 @@ def warm_wide_kernels(device, dtype=torch.bfloat16) -> None:
     kernels the configured limits can route to are launched, and the caller's wide row
     thresholds are restored afterwards."""
     dev = torch.device(device)
-    top = fused_max_rows(True, False)
+    top = fused_max_rows()
     if dev.type != "cuda" or top <= SKINNY_MAX_M:
         return
     ensure_splitk_workspace(dev)
     w = preshuffle(torch.zeros(128, 256, dtype=dtype, device=dev))
-    prev = [int(v) for v in _native().get_wide_min_rows()]
+    prev = list(_wide_min_rows)
     set_wide_min_rows(1, 1)
     try:
-        for mt in range(1, 9):
-            if 16 * mt <= min(top, 128):
-                linear(torch.zeros(16 * mt, 256, dtype=dtype, device=dev), w, preshuffled=True)
-        if top > 128:
+        for rows in range(16, min(top, WIDE_ROWS) + 1, 16):
+            linear(torch.zeros(rows, 256, dtype=dtype, device=dev), w, preshuffled=True)
+        if top > WIDE_ROWS:
             x = torch.zeros(144, 256, dtype=dtype, device=dev)
             for b in MIDM_BUILT:
                 set_midm_plan(b, 1)
@@ -564,6 +591,7 @@ def set_wide_min_rows(m: int = 17, m_silu: int = 12) -> None:
     wide small-M kernel; calls over 32 rows always do.  Defaults = the measured crossover
     (profiles/r5_wide_vs_skinny.txt); 33 / 33 keeps <= 32 rows on the 16-row-tile GEMVs."""
     _native().set_wide_min_rows(int(m), int(m_silu))
+    _wide_min_rows[:] = (max(1, int(m)), max(1, int(m_silu)))  # as the library clamps them
 
 
 def preshuffle(w: torch.Tensor, rowmap: str = "plain") -> torch.Tensor:
@@ -810,9 +838,10 @@ def linear(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor | None = Non
     fp8 = w_scale is not None
     if fp8:
         preshuffled = True
-    if preshuffled and not skinny_ok(x, w, preshuffled, fp8):
+    fused = skinny_ok(x, w, preshuffled, fp8)
+    if preshuffled and not fused:
         raise ValueError("pre-shuffled weights need the skinny (decode) path")
-    if skinny_ok(x, w, preshuffled, fp8):
+    if fused:
         ksplit = _ksplit(proj, x, ksplit, w.shape[0] // 16)
         if residual is not None:
             _native().skinny_gemm(residual, x, w, residual, waves or SKINNY_WAVES, preshuffled,

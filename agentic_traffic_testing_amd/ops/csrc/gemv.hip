@@ -31,6 +31,7 @@
 //               (sampler fused into the LM head; `sample_finalize` reduces a row's
 //               partials to its token id with one workgroup per row)
 #include <cstdlib>
+#include <type_traits>
 
 #include "common.h"
 #include "kernels.h"
@@ -75,36 +76,32 @@ static int nt_weights() {
 template <int WAVES, int UNROLL, int MT, int EPI>
 static void launch_t(int dtype, dim3 grid, hipStream_t st, const SkinnyParams& p) {
   const int mode = nt_weights();
-  const bool shuffled = p.ps || p.wscale != nullptr;
-  const bool nt = shuffled ? mode != 0 : mode == 1;
-  const dim3 blk(WAVES * 64);
-#define ATTA_SK(T_, U_, NT_, PS_, W8_) \
-  skinny_kernel<T_, WAVES, U_, MT, EPI, NT_, PS_, W8_><<<grid, blk, 0, st>>>(p)
-  if (p.wscale != nullptr) {
-    // fp8 weights (pre-shuffled by construction): a 16-byte lane load carries two K steps,
-    // so the stage is twice as deep to keep the same bytes in flight per wave.  (Twice that
-    // again - a wave's whole K slice in flight in its first two stages - measured slower in
-    // situ: fp8 bench 986 vs 1022 tok/s, profiles/r2_ab_fp8_stage_depth.txt.)
-    constexpr int U8 = UNROLL * 2;
-    if (dtype == 0) {
-      if (nt) ATTA_SK(__bf16, U8, true, true, true); else ATTA_SK(__bf16, U8, false, true, true);
-    } else {
-      if (nt) ATTA_SK(_Float16, U8, true, true, true); else ATTA_SK(_Float16, U8, false, true, true);
-    }
-    return;
-  }
-  if (dtype == 0) {
-    if (p.ps && nt) ATTA_SK(__bf16, UNROLL, true, true, false);
-    else if (p.ps) ATTA_SK(__bf16, UNROLL, false, true, false);
-    else if (nt) ATTA_SK(__bf16, UNROLL, true, false, false);
-    else ATTA_SK(__bf16, UNROLL, false, false, false);
-  } else {
-    if (p.ps && nt) ATTA_SK(_Float16, UNROLL, true, true, false);
-    else if (p.ps) ATTA_SK(_Float16, UNROLL, false, true, false);
-    else if (nt) ATTA_SK(_Float16, UNROLL, true, false, false);
-    else ATTA_SK(_Float16, UNROLL, false, false, false);
-  }
-#undef ATTA_SK
+  const bool w8 = p.wscale != nullptr, ps = p.ps || w8;
+  const bool nt = ps ? mode != 0 : mode == 1;
+  // runtime (dtype, nt, layout) -> template arguments: {bf16, fp16} x {nt, cached} x
+  // {row-major, pre-shuffled, fp8}.  fp8 weights are pre-shuffled by construction and a
+  // 16-byte lane load carries two K steps, so their stage is twice as deep to keep the same
+  // bytes in flight per wave.  (Twice that again - a wave's whole K slice in flight in its
+  // first two stages - measured slower in situ: fp8 bench 986 vs 1022 tok/s,
+  // profiles/r2_ab_fp8_stage_depth.txt.)
+  auto launch = [&](auto t, auto nt_, auto ps_, auto w8_) {
+    constexpr bool W8 = decltype(w8_)::value;
+    skinny_kernel<decltype(t), WAVES, W8 ? UNROLL * 2 : UNROLL, MT, EPI, decltype(nt_)::value,
+                  decltype(ps_)::value, W8><<<grid, dim3(WAVES * 64), 0, st>>>(p);
+  };
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  auto by_layout = [&](auto t, auto nt_) {
+    if (w8) launch(t, nt_, yes, yes);
+    else if (ps) launch(t, nt_, yes, no);
+    else launch(t, nt_, no, no);
+  };
+  auto by_nt = [&](auto t) {
+    if (nt) by_layout(t, yes);
+    else by_layout(t, no);
+  };
+  if (dtype == 0) by_nt(__bf16{});
+  else by_nt(_Float16{});
 }
 
 template <int EPI>
@@ -199,9 +196,8 @@ static unsigned long long* take_trace() {
   return t;
 }
 
-// Rows past the 16-row-tile GEMV (33-128, pre-shuffled 16-bit weights) go to the wide
-// small-M kernel (wide.hip); its (waves, split) plan is automatic unless overridden for the
-// NEXT such launch by atta_set_wide_plan (tuning sweeps).
+// The wide small-M kernel (wide.hip): its (waves, split) plan is automatic unless overridden
+// for the NEXT such launch by atta_set_wide_plan (tuning sweeps).
 int atta_wide_launch(SkinnyParams& p, int epi, int ntiles, int waves, int ksplit, int dtype,
                      const float* sk_ws, int* sk_counters, int64_t ws_floats, int n_counters,
                      hipStream_t stream);
@@ -210,9 +206,8 @@ void atta_set_wide_plan(int waves, int ksplit) {
   g_wide_waves = waves;
   g_wide_ksplit = ksplit;
 }
-static int wide(SkinnyParams& p, int epi, int ntiles, int dtype, hipStream_t stream);
-// the wide kernel takes every call over 32 rows and, for pre-shuffled 16-bit weights, calls
-// from g_wide_min_m rows (gate_up + SiLU: g_wide_min_m_silu).  At 17-32 rows the 16-row-tile
+// Pre-shuffled 16-bit calls run the wide kernel from g_wide_min_m rows (gate_up + SiLU:
+// g_wide_min_m_silu), see route().  At 17-32 rows the 16-row-tile
 // GEMVs re-read x per weight tile in two row blocks (per layer 120-137 us vs 95-98 us wide);
 // at 12-16 rows only gate_up gains (43.3 / 48.2 -> 39.3 / 39.1 us); at <= 8 rows (decode)
 // the GEMVs win every projection (profiles/r5_wide_vs_skinny.txt)
@@ -225,23 +220,34 @@ void atta_get_wide_min_rows(int* m, int* m_silu) {
   *m = g_wide_min_m;
   *m_silu = g_wide_min_m_silu;
 }
-// pre-shuffled 16-bit calls of up to this many rows run the wide (<= 128) or mid-M kernels
-constexpr int kMidmMaxM = 8192;
-// rows one call may carry: row-major weights the 16-row-tile GEMV (<= 32); pre-shuffled
-// 16-bit or fp8 weights also the wide (<= 128) and mid-M kernels
-static int max_rows(int ps, const float* wscale) {
-  (void)wscale;
-  return !ps ? 32 : kMidmMaxM;
-}
-static bool use_wide(int M, int ps, const float* wscale, bool silu = false) {
-  return M > 32 ||
-         (ps && wscale == nullptr && M >= (silu ? g_wide_min_m_silu : g_wide_min_m));
-}
 
-static int skinny_checks(int M, int K, int waves) {
-  if (M < 1 || M > 32) return -1;
-  if (K % (32 * waves) != 0) return -1;
-  return 0;
+// Which kernel runs M rows of a weight layout with an epilogue - the one routing table of
+// the library (ops.fused_kernel is the same table under the Python-side row policy).
+// min = g_wide_min_m (17), for EPI_SILU g_wide_min_m_silu (12):
+//
+//   weights               epilogue          rows               kernel
+//   any                   any               M < 1              None
+//   row-major 16-bit      any               1 - 32             Skinny
+//   row-major 16-bit      any               > 32               None
+//   pre-shuffled 16-bit   any               1 .. min - 1       Skinny
+//   pre-shuffled 16-bit   any               min .. 128         Wide
+//   pre-shuffled 16-bit   any but SAMPLE    129 .. kMidmMaxM   MidM
+//   fp8 (pre-shuffled)    any but SAMPLE    1 - 32             Skinny
+//   fp8                   any but SAMPLE    33 - 128           Wide
+//   fp8                   any but SAMPLE    129 .. kMidmMaxM   MidM
+//   any                   SAMPLE            > 128              None   (no sampler epilogue in
+//   fp8                   SAMPLE            > 32               None    those builds)
+//   any                   the push variant  1 - 32             Skinny (routes as row-major:
+//   any                   the push variant  > 32               None    the GEMV alone pushes)
+enum class Route { None, Skinny, Wide, MidM };
+static Route route(int M, bool ps, bool w8, int epi) {
+  if (M < 1) return Route::None;
+  if (!ps) return M <= kSkinnyMaxM ? Route::Skinny : Route::None;
+  const int wide_min = epi == EPI_SILU ? g_wide_min_m_silu : g_wide_min_m;
+  if (M <= kSkinnyMaxM && (w8 || M < wide_min)) return Route::Skinny;
+  if (epi == EPI_SAMPLE && (w8 || M > kWideMaxM)) return Route::None;
+  if (M <= kWideMaxM) return Route::Wide;
+  return M <= kMidmMaxM ? Route::MidM : Route::None;
 }
 
 // Split-K workspace per device (ops.set_splitk_workspace): fp32 partial slots + one arrival
@@ -260,22 +266,10 @@ int atta_set_splitk_ws(int device, float* ws, int* counters, int64_t ws_floats, 
   return 0;
 }
 
-int atta_midm_launch(SkinnyParams& p, int epi, int ntiles, int dtype, float* sk_ws,
-                     int64_t ws_floats, hipStream_t stream);
-static int wide(SkinnyParams& p, int epi, int ntiles, int dtype, hipStream_t stream) {
+static const SplitKWs* splitk_ws() {  // the current device's, or nullptr
   int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -2;
-  const SplitKWs& w = g_splitk[dev];
-  if (p.M > 128) {
-    // past the wide kernel's 8 row blocks: the mid-M kernel (midm.hip, row-blocked grid)
-    p.wg_trace = nullptr;
-    return atta_midm_launch(p, epi, ntiles, dtype, w.ws, w.ws_floats, stream);
-  }
-  const int waves = g_wide_waves, ksplit = g_wide_ksplit;
-  g_wide_waves = g_wide_ksplit = 0;
-  p.wg_trace = take_trace();  // 4 stamps per workgroup here (wide.hip)
-  return atta_wide_launch(p, epi, ntiles, waves, ksplit, dtype, w.ws, w.counters, w.ws_floats,
-                          w.n_counters, stream);
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return nullptr;
+  return &g_splitk[dev];
 }
 
 // Resolve the split for one launch: waves fitted to the K slice (fp8: 64-wide granule), the
@@ -289,16 +283,80 @@ static int setup_split(SkinnyParams& p, int& waves, int ksplit, int tiles, bool 
   if ((p.K / ksplit) % (gran * waves) != 0) return -1;
   p.ksplit = ksplit;
   if (ksplit == 1) return 0;
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return -2;
-  const SplitKWs& w = g_splitk[dev];
-  const int64_t slot = static_cast<int64_t>(p.M <= 16 ? 16 : 32) * 17;
-  if (w.ws == nullptr || tiles > w.n_counters ||
-      static_cast<int64_t>(tiles) * ksplit * slot > w.ws_floats)
+  const SplitKWs* w = splitk_ws();
+  if (w == nullptr) return -2;
+  // one slot per (tile, slice): the launch's row blocks (16 or kSkinnyMaxM rows) x 17 floats
+  const int64_t slot = static_cast<int64_t>(p.M <= 16 ? 16 : kSkinnyMaxM) * 17;
+  if (w->ws == nullptr || tiles > w->n_counters ||
+      static_cast<int64_t>(tiles) * ksplit * slot > w->ws_floats)
     return -2;
-  p.sk_ws = w.ws;
-  p.sk_counters = w.counters;
+  p.sk_ws = w->ws;
+  p.sk_counters = w->counters;
   return 0;
+}
+
+// The 16-row-tile GEMV for filled params: split, grid, pending timeline probe, launch.
+template <int EPI>
+static int launch_skinny(SkinnyParams& p, int tiles, int waves, int ksplit, int dtype,
+                         hipStream_t stream) {
+  if (const int rc = setup_split(p, waves, ksplit, tiles, p.wscale != nullptr)) return rc;
+  const dim3 grid(tiles, p.ksplit);
+  p.wg_trace = take_trace();
+  launch_epi<EPI>(dtype, p.M <= 16 ? 1 : 2, waves, grid, stream, p);
+  return static_cast<int>(hipGetLastError());
+}
+
+int atta_midm_launch(SkinnyParams& p, int epi, int ntiles, int dtype, float* sk_ws,
+                     int64_t ws_floats, hipStream_t stream);
+// The wide small-M kernel (wide.hip) for filled params: the next-launch plan override and
+// the pending timeline probe are consumed here.
+static int launch_wide(SkinnyParams& p, int epi, int tiles, int dtype, hipStream_t stream) {
+  const SplitKWs* w = splitk_ws();
+  if (w == nullptr) return -2;
+  const int waves = g_wide_waves, ksplit = g_wide_ksplit;
+  g_wide_waves = g_wide_ksplit = 0;
+  p.wg_trace = take_trace();  // 4 stamps per workgroup here (wide.hip)
+  return atta_wide_launch(p, epi, tiles, waves, ksplit, dtype, w->ws, w->counters, w->ws_floats,
+                          w->n_counters, stream);
+}
+
+// The mid-M kernel (midm.hip, row-blocked grid).  It has no timeline probe: a pending one
+// stays pending for the next GEMV or wide launch.
+static int launch_midm(SkinnyParams& p, int epi, int tiles, int dtype, hipStream_t stream) {
+  const SplitKWs* w = splitk_ws();
+  if (w == nullptr) return -2;
+  p.wg_trace = nullptr;
+  return atta_midm_launch(p, epi, tiles, dtype, w->ws, w->ws_floats, stream);
+}
+
+// Launch filled params on the kernel route() names; tiles: 16-column weight tiles; waves /
+// ksplit: the caller's plan for the 16-row-tile GEMV (the other two plan for themselves).
+template <int EPI>
+static int launch_routed(SkinnyParams& p, int tiles, int waves, int ksplit, int dtype,
+                         hipStream_t stream) {
+  switch (route(p.M, p.ps != 0, p.wscale != nullptr, EPI)) {
+    case Route::Skinny: return launch_skinny<EPI>(p, tiles, waves, ksplit, dtype, stream);
+    case Route::Wide: return launch_wide(p, EPI, tiles, dtype, stream);
+    case Route::MidM: return launch_midm(p, EPI, tiles, dtype, stream);
+    case Route::None: break;
+  }
+  return -1;
+}
+
+// The fields every entry point fills the same way.
+static SkinnyParams base_params(const void* x, const void* w, int M, int N, int K,
+                                int64_t x_stride, float eps, int ps, const float* wscale) {
+  SkinnyParams p{};
+  p.x = static_cast<const uint16_t*>(x);
+  p.w = static_cast<const uint16_t*>(w);
+  p.M = M;
+  p.N = N;
+  p.K = K;
+  p.x_stride = x_stride;
+  p.eps = eps;
+  p.ps = ps;
+  p.wscale = wscale;
+  return p;
 }
 
 int atta_skinny_gemm(void* y, const void* x, const void* w, const void* residual, int M, int N,
@@ -306,40 +364,15 @@ int atta_skinny_gemm(void* y, const void* x, const void* w, const void* residual
                      int ksplit, const float* wscale, int dtype, hipStream_t stream) {
   const int ps = (dtype & kPreshuffled) ? 1 : 0;
   dtype &= ~kPreshuffled;
-  if (M < 1 || M > max_rows(ps, wscale) || N % 16 != 0) return -1;
-  SkinnyParams p{};
-  p.ps = ps;
-  p.wscale = wscale;
-  p.x = static_cast<const uint16_t*>(x);
-  p.w = static_cast<const uint16_t*>(w);
-  p.M = M;
-  p.N = N;
-  p.K = K;
-  p.x_stride = x_stride;
-  p.eps = 0.f;
-  if (use_wide(M, ps, wscale)) {
-    if (residual != nullptr && residual != y) return -1;
-    p.y = static_cast<uint16_t*>(y);
-    p.y_stride = residual != nullptr ? res_stride : y_stride;
-    return wide(p, residual != nullptr ? EPI_RESADD : EPI_PLAIN, N / 16, dtype, stream);
-  }
-  if (const int rc = setup_split(p, waves, ksplit, N / 16, wscale != nullptr)) return rc;
-  const int mt = M <= 16 ? 1 : 2;
-  dim3 grid(N / 16, p.ksplit);
-  p.wg_trace = take_trace();
-  if (residual != nullptr) {
-    // y := residual + x W^T, computed in place on the residual buffer when y == residual;
-    // otherwise copy semantics are not supported (callers pass y == residual).
-    if (residual != y) return -1;
-    p.y = static_cast<uint16_t*>(y);
-    p.y_stride = res_stride;
-    launch_epi<EPI_RESADD>(dtype, mt, waves, grid, stream, p);
-  } else {
-    p.y = static_cast<uint16_t*>(y);
-    p.y_stride = y_stride;
-    launch_epi<EPI_PLAIN>(dtype, mt, waves, grid, stream, p);
-  }
-  return static_cast<int>(hipGetLastError());
+  // y := residual + x W^T is computed in place on the residual buffer: copy semantics are
+  // not supported (callers pass y == residual)
+  if (N % 16 != 0 || (residual != nullptr && residual != y)) return -1;
+  SkinnyParams p = base_params(x, w, M, N, K, x_stride, 0.f, ps, wscale);
+  p.y = static_cast<uint16_t*>(y);
+  p.y_stride = residual != nullptr ? res_stride : y_stride;
+  return residual != nullptr
+             ? launch_routed<EPI_RESADD>(p, N / 16, waves, ksplit, dtype, stream)
+             : launch_routed<EPI_PLAIN>(p, N / 16, waves, ksplit, dtype, stream);
 }
 
 // Row-parallel TP GEMV with the all-reduce push fused into its epilogue: x W^T of this rank's
@@ -351,30 +384,18 @@ int atta_skinny_gemm_push(const void* x, const void* w, int M, int N, int K, int
                           hipStream_t stream) {
   const int ps = (dtype & kPreshuffled) ? 1 : 0;
   dtype &= ~kPreshuffled;
-  if (M < 1 || M > 32 || N % 16 != 0) return -1;
+  // only the 16-row-tile GEMV has the push epilogue: whatever the layout, the call routes
+  // as row-major weights do
+  if (route(M, false, wscale != nullptr, EPI_PLAIN) != Route::Skinny || N % 16 != 0) return -1;
   if ((world != 2 && world != 4 && world != 8) || rank < 0 || rank >= world ||
       static_cast<int64_t>(M) * N > max_elems)
     return -1;
-  SkinnyParams p{};
-  p.ps = ps;
-  p.wscale = wscale;
-  p.x = static_cast<const uint16_t*>(x);
-  p.w = static_cast<const uint16_t*>(w);
-  p.M = M;
-  p.N = N;
-  p.K = K;
-  p.x_stride = x_stride;
-  p.eps = 0.f;
+  SkinnyParams p = base_params(x, w, M, N, K, x_stride, 0.f, ps, wscale);
   for (int q = 0; q < world; ++q) p.push_base[q] = static_cast<uint8_t*>(bases[q]);
   p.push_world = world;
   p.push_rank = rank;
   p.push_max_elems = max_elems;
-  if (const int rc = setup_split(p, waves, ksplit, N / 16, wscale != nullptr)) return rc;
-  const int mt = M <= 16 ? 1 : 2;
-  dim3 grid(N / 16, p.ksplit);
-  p.wg_trace = take_trace();
-  launch_epi<EPI_PLAIN>(dtype, mt, waves, grid, stream, p);
-  return static_cast<int>(hipGetLastError());
+  return launch_skinny<EPI_PLAIN>(p, N / 16, waves, ksplit, dtype, stream);
 }
 
 int atta_fused_qkv_rope(void* q_out, void* k_cache, void* v_cache, const void* x, const void* w,
@@ -384,22 +405,13 @@ int atta_fused_qkv_rope(void* q_out, void* k_cache, void* v_cache, const void* x
                         int dtype, hipStream_t stream) {
   const int ps = (dtype & kPreshuffled) ? 1 : 0;
   dtype &= ~kPreshuffled;
-  if (M < 1 || M > max_rows(ps, wscale)) return -1;
   int shift = 0;
   while ((1 << shift) < block_size) ++shift;
   if ((1 << shift) != block_size) return -1;
-  SkinnyParams p{};
-  p.ps = ps;
-  p.wscale = wscale;
-  p.x = static_cast<const uint16_t*>(x);
-  p.w = static_cast<const uint16_t*>(w);
+  SkinnyParams p = base_params(x, w, M, (n_q_heads + 2 * n_kv_heads) * 128, K, x_stride, eps,
+                               ps, wscale);
   p.y = static_cast<uint16_t*>(q_out);
-  p.x_stride = x_stride;
   p.y_stride = q_stride;
-  p.M = M;
-  p.K = K;
-  p.N = (n_q_heads + 2 * n_kv_heads) * 128;
-  p.eps = eps;
   p.k_cache = static_cast<uint16_t*>(k_cache);
   p.v_cache = static_cast<uint16_t*>(v_cache);
   p.positions = positions;
@@ -408,12 +420,7 @@ int atta_fused_qkv_rope(void* q_out, void* k_cache, void* v_cache, const void* x
   p.n_q_heads = n_q_heads;
   p.n_kv_heads = n_kv_heads;
   p.bs_shift = shift;
-  if (use_wide(M, ps, wscale)) return wide(p, EPI_QKVROPE, p.N / 16, dtype, stream);
-  if (const int rc = setup_split(p, waves, ksplit, p.N / 16, wscale != nullptr)) return rc;
-  dim3 grid(p.N / 16, p.ksplit);
-  p.wg_trace = take_trace();
-  launch_epi<EPI_QKVROPE>(dtype, M <= 16 ? 1 : 2, waves, grid, stream, p);
-  return static_cast<int>(hipGetLastError());
+  return launch_routed<EPI_QKVROPE>(p, p.N / 16, waves, ksplit, dtype, stream);
 }
 
 int atta_fused_gate_up_silu(void* out, const void* x, const void* w, int M, int K, int inter,
@@ -421,26 +428,12 @@ int atta_fused_gate_up_silu(void* out, const void* x, const void* w, int M, int 
                             int ksplit, const float* wscale, int dtype, hipStream_t stream) {
   const int ps = (dtype & kPreshuffled) ? 1 : 0;
   dtype &= ~kPreshuffled;
-  if (M < 1 || M > max_rows(ps, wscale) || inter % 8 != 0) return -1;
-  SkinnyParams p{};
-  p.ps = ps;
-  p.wscale = wscale;
-  p.x = static_cast<const uint16_t*>(x);
-  p.w = static_cast<const uint16_t*>(w);
+  if (inter % 8 != 0) return -1;
+  SkinnyParams p = base_params(x, w, M, 2 * inter, K, x_stride, eps, ps, wscale);
   p.y = static_cast<uint16_t*>(out);
-  p.x_stride = x_stride;
   p.y_stride = out_stride;
-  p.M = M;
-  p.K = K;
-  p.N = 2 * inter;
   p.inter = inter;
-  p.eps = eps;
-  if (use_wide(M, ps, wscale, true)) return wide(p, EPI_SILU, inter / 8, dtype, stream);
-  if (const int rc = setup_split(p, waves, ksplit, inter / 8, wscale != nullptr)) return rc;
-  dim3 grid(inter / 8, p.ksplit);
-  p.wg_trace = take_trace();
-  launch_epi<EPI_SILU>(dtype, M <= 16 ? 1 : 2, waves, grid, stream, p);
-  return static_cast<int>(hipGetLastError());
+  return launch_routed<EPI_SILU>(p, inter / 8, waves, ksplit, dtype, stream);
 }
 
 int atta_fused_lm_head_sample(int64_t* tokens, unsigned long long* keys, const void* x,
@@ -450,34 +443,16 @@ int atta_fused_lm_head_sample(int64_t* tokens, unsigned long long* keys, const v
                               int waves, const float* wscale, int dtype, hipStream_t stream) {
   const int ps = (dtype & kPreshuffled) ? 1 : 0;
   dtype &= ~kPreshuffled;
-  waves = fit_waves(waves, K, wscale != nullptr);
-  const bool wd = use_wide(M, ps, wscale) && ps && wscale == nullptr && M <= 128;
-  if ((!wd && skinny_checks(M, K, waves)) || N % 16 != 0) return -1;
-  SkinnyParams p{};
-  p.ps = ps;
-  p.wscale = wscale;
-  if (wscale != nullptr && (K / waves) % 64 != 0) return -1;
-  p.x = static_cast<const uint16_t*>(x);
-  p.w = static_cast<const uint16_t*>(w);
-  p.x_stride = x_stride;
-  p.M = M;
-  p.N = N;
-  p.K = K;
-  p.eps = eps;
+  if (N % 16 != 0) return -1;
+  SkinnyParams p = base_params(x, w, M, N, K, x_stride, eps, ps, wscale);
   p.keys = keys;
   p.key_stride = N / 16;
   p.vocab_offset = vocab_offset;
-  p.ksplit = 1;
   p.temperature = temperature;
   p.seeds = seeds;
   p.steps = steps;
-  if (wd) {
-    if (const int rc = wide(p, EPI_SAMPLE, N / 16, dtype, stream)) return rc;
-  } else {
-    dim3 grid(N / 16);
-    p.wg_trace = take_trace();
-    launch_epi<EPI_SAMPLE>(dtype, M <= 16 ? 1 : 2, waves, grid, stream, p);
-  }
+  // unsplit: the partial keys of a (row, tile) come from one workgroup
+  if (const int rc = launch_routed<EPI_SAMPLE>(p, N / 16, waves, 1, dtype, stream)) return rc;
   if (finalize == 1)
     sample_finalize_kernel<false><<<M, kFinThreads, 0, stream>>>(tokens, keys, N / 16);
   else if (finalize == 2)

@@ -157,7 +157,7 @@ int atta_midm_plan(int M, int ntiles, int K, int epi, int64_t ws_floats, int* bm
 // (SiLU: inter / 8).  Returns 0, -1 (unsupported shape / plan) or -2 (split-K workspace).
 int atta_midm_launch(SkinnyParams& p, int epi, int ntiles, int dtype, float* sk_ws,
                      int64_t ws_floats, hipStream_t stream) {
-  if (p.M < 1 || p.K % midm::kKC != 0 || !p.ps) return -1;
+  if (p.M < 1 || p.M > kMidmMaxM || p.K % midm::kKC != 0 || !p.ps) return -1;
   if (epi != EPI_PLAIN && epi != EPI_RESADD && epi != EPI_QKVROPE && epi != EPI_SILU) return -1;
   const bool can_split = epi == EPI_PLAIN || epi == EPI_RESADD;
   int bmt = g_midm_bmt, S = g_midm_ksplit;

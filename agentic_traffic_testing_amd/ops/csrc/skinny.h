@@ -8,6 +8,13 @@
 
 namespace atta {
 
+// Most rows per call of the three weight-streaming GEMMs (who runs what: route() in
+// gemv.hip; ops.SKINNY_ROWS / WIDE_ROWS / MIDM_ROWS mirror them for ops.fused_kernel)
+constexpr int kSkinnyMaxM = 32;   // 16-row-tile GEMV: two MFMA row blocks
+constexpr int kWideMaxM = 128;    // wide small-M kernel: eight row blocks in one workgroup
+constexpr int kMidmMaxM = 8192;   // mid-M kernel: what the library accepts (ops.MIDM_MAX_M,
+                                  // the routing policy, stops at 1024 by default)
+
 enum Epi {
   EPI_PLAIN = 0,
   EPI_RESADD = 1,

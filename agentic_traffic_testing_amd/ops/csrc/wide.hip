@@ -210,7 +210,7 @@ void atta_set_splitk_half(int on) { g_sk_half = on ? 1 : 0; }
 int atta_wide_launch(SkinnyParams& p, int epi, int ntiles, int waves, int ksplit, int dtype,
                      const float* sk_ws, int* sk_counters, int64_t ws_floats, int n_counters,
                      hipStream_t stream) {
-  if (p.M < 1 || p.M > 128 || p.K % wide::kKC != 0 || !p.ps) return -1;
+  if (p.M < 1 || p.M > kWideMaxM || p.K % wide::kKC != 0 || !p.ps) return -1;
   const bool w8 = p.wscale != nullptr;  // fp8 weights (the W8 builds)
   // waves 14 / 16 / 17 / 18 in an explicit plan = 4 / 6 / 7 / 8 waves x two tiles per wave
   // (measured slower and not built: such a plan returns -1 from the launcher)

@@ -27,6 +27,8 @@ from dataclasses import dataclass
 import torch
 import torch.distributed as dist
 
+from .. import ops
+
 
 @dataclass
 class TPComm:
@@ -64,7 +66,8 @@ class TPComm:
         """Can a row-parallel decode GEMV push its product straight into the peers'
         receive slots (IPC path, fused push)?"""
         return (self.size > 1 and self.ipc is not None and self.fused_push
-                and rows <= 32 and self.ipc.push_eligible(rows, n_out))  # GEMV: <= 32 rows
+                and ops.fused_kernel(rows, False, epi="push") is not None
+                and self.ipc.push_eligible(rows, n_out))
 
     fused_push: bool = True
 

@@ -283,10 +283,32 @@ def test_wide_fused_decode_matches_oracle(nseq):
                                  num_kv_blocks=2048, max_num_seqs=nseq,
                                  max_num_batched_tokens=4096,
                                  graph_batch_sizes=(1, 2, 4, 8, 16, 32, 64, 128)))
-    assert eng.runner.fused_decode and eng.runner.model.decode_fusable(nseq)
+    assert eng.runner.fused_decode and eng.runner.model.decode_step_fusable(nseq)
     _check(eng, prompts, n=4, tol_logit=0.25)
     bucket = 64 if nseq <= 64 else 128
     assert any(k[0] == bucket for k in eng.runner.graphs), sorted(eng.runner.graphs)
+    assert eng.runner.graph_steps > 0
+
+
+@pytest.mark.gpu
+def test_engine_decodes_past_128_sequences():
+    """more sequences than the fused LM head + sampler takes (128).  The
+    256 bucket is captured at start-up and replayed on the library path - the layer
+    projections of a 136-row step could run the mid-M kernel, a whole forward_decode step
+    cannot - and every generated position matches the fp32 dense oracle teacher-forced."""
+    nseq = 136
+    rng = np.random.default_rng(nseq)
+    prompts = [rng.integers(300, 30000, size=int(n)).tolist()
+               for n in rng.integers(3, 21, size=nseq)]
+    eng = LLMEngine(EngineConfig(model="small", device="cuda", max_model_len=512,
+                                 num_kv_blocks=4096, max_num_seqs=nseq,
+                                 max_num_batched_tokens=4096,
+                                 graph_batch_sizes=(1, 2, 4, 8, 16, 32, 64, 128, 256)))
+    m = eng.runner.model
+    assert m.decode_step_fusable(128) and not m.decode_step_fusable(nseq)
+    assert m.proj_fusable(nseq)
+    _check(eng, prompts, n=2, tol_logit=0.25)
+    assert any(k[0] == 256 for k in eng.runner.graphs), sorted(eng.runner.graphs)
     assert eng.runner.graph_steps > 0
 
 

@@ -620,7 +620,7 @@ def test_fp8_fused_past_32_rows_prefill_and_decode(tp):
     try:
         r = eng.runner
         m = r.model
-        assert m.quant == "fp8" and m.small_prefill_ok(96) and m.decode_fusable(48)
+        assert m.quant == "fp8" and m.small_prefill_ok(96) and m.decode_step_fusable(48)
         assert not m.midm_route(96) and not m.midm_fp8_ok(96)
         steps0, g0 = r.steps, r.graph_steps
         got = [o.token_ids for o in eng.generate(prompts, greedy)]
