@@ -335,7 +335,7 @@ class ModelRunner:
             # steps the fused small-prefill path takes (<= SKINNY_MAX_M rows) stay unpadded:
             # its GEMVs read every row of x per weight tile (17 rows padded to 32 doubled
             # gate_up: 80 vs ~40 us)
-            if not self.model.small_prefill_ok(rows):
+            if self.model.step_plan(rows).pad_rows:
                 pad_tokens = bucket_rows(rows)
         d = self.bm.build_batch(ids, qs, ql, self.bt_width,
                                 self.tile_tokens if tiles else 0, batch.num_decode, pad_tokens,

@@ -19,7 +19,6 @@ from __future__ import annotations
 
 import json
 import math
-import os
 from dataclasses import dataclass
 from pathlib import Path
 
@@ -28,6 +27,8 @@ import torch.nn.functional as F
 
 from .. import ops
 from ..config import ModelConfig
+from . import step_plan as sp
+from .step_plan import FUSED, GEMM, GEMM_SPLITK
 from ..ops import reference as ref
 
 DTYPES = {"bfloat16": torch.bfloat16, "bf16": torch.bfloat16, "float16": torch.float16,
@@ -118,12 +119,9 @@ class LlamaModel:
         self.cos_sin = ref.rope_cos_sin(cfg.head_dim, min(cfg.max_position_embeddings, 1 << 17),
                                         cfg.rope_theta, cfg.rope_scaling, device=self.device)
         self.g = self.n_heads // self.n_kv_heads
-        # every projection's K in whole wave steps of the weight-streaming kernels (16-bit
-        # GEMVs: K % 128 = 4 waves x 32; fp8: K % 256 = 4 waves x 64) - proj_fusable
-        step = 256 if self.quant == "fp8" else 128
-        self._proj_dims_ok = (self.device.type == "cuda" and cfg.hidden_size % step == 0
-                              and self.inter % step == 0
-                              and (self.n_heads * self.head_dim) % step == 0)
+        self._proj_dims_ok = sp.proj_dims_ok(self.device.type == "cuda", self.quant,
+                                             cfg.hidden_size, self.n_heads * self.head_dim,
+                                             self.inter)  # proj_fusable
         if self.head_dim != 128 and self.device.type == "cuda":
             raise ValueError("HIP attention kernels require head_dim 128")
 
@@ -300,16 +298,6 @@ class LlamaModel:
                    l.gate_up_s, l.down_s]
         return sum(t.numel() * t.element_size() for t in ts if t is not None)
 
-    @staticmethod
-    def _proj(x, w, scale, residual=None):
-        """Prefill / generic projection: fp8 weights go through the fp8 GEMM path."""
-        if scale is None:
-            return ops.linear(x, w, residual=residual)
-        y = ops.linear_fp8(x, w, scale)
-        if residual is not None:
-            return residual.add_(y)
-        return y
-
     def _all_reduce(self, x: torch.Tensor) -> torch.Tensor:
         if self.tp_size > 1:
             self.tp_group.all_reduce(x)
@@ -329,43 +317,35 @@ class LlamaModel:
         residual = ops.embed(self.embed, input_ids, prev_tokens, feed_prev)
         T = residual.shape[0]
         nq, nkv, D = self.n_heads, self.n_kv_heads, self.head_dim
-        # fp8 weights on the GPU: every projection is ONE fp8 GEMM with row-wise scales whose
-        # activation operand comes quantised out of the norm / SiLU-mul kernel that produced it
-        fp8 = self.quant == "fp8" and self.device.type == "cuda"
         dt = residual.dtype
-        pending = None  # fp8: the previous down_proj output, added by the next norm kernel
-        # small steps (<= 32 rows: cached-prompt planning prefills, short chunks) run the fused
-        # decode kernels - RMSNorm folded into the skinny GEMVs over the pre-shuffled weights,
-        # RoPE + KV write in the QKV epilogue, SiLU-mul in gate_up - around the prefill
-        # attention: 5 launches per layer at weight-stream speed instead of ~9 with the
-        # row-major skinny / library GEMMs (17 rows: 168 -> ~80 us of GEMMs per layer,
-        # profiles/r4_small_prefill_fused.txt)
-        # fp8 steps of 129.. rows in the MIDM_FP8_ROWS range run every projection on the
-        # mid-M kernel's W8 builds (all or nothing: the library fp8 chain defers each down
-        # product into the next layer's norm-quant kernel, which a fused qkv cannot take)
-        small = self.small_prefill_ok(T) or (fp8 and self.midm_fp8_ok(T))
-        # 129..640-row steps (uncached burst / planning prefills): per projection, the mid-M
-        # kernel (ops/csrc/midm.h, fused epilogues) where it beats the tuned library GEMM +
-        # separate norm / RoPE / SiLU kernels, the library elsewhere (midm_route)
-        mid = {} if (small or fp8) else self.midm_route(T)
+        pending = None  # fp8 chain: the previous down_proj output, added by the next norm kernel
+        # one backend per projection, the same for every layer (step_plan.py has the table):
+        # small steps run the fused decode kernels around the prefill attention - 5 launches per
+        # layer at weight-stream speed instead of ~9 with the row-major skinny / library GEMMs
+        # (17 rows: 168 -> ~80 us of GEMMs per layer, profiles/r4_small_prefill_fused.txt);
+        # 129..640-row steps (uncached burst / planning prefills) run the mid-M kernel per
+        # projection where it beats the tuned library GEMM + separate kernels; fp8 steps past
+        # the fused rows run the activation-quantised chain: every projection is ONE fp8 GEMM
+        # with row-wise scales whose activation operand comes quantised out of the norm /
+        # SiLU-mul kernel that produced it
+        plan = self.step_plan(T)
         for li, L in enumerate(self.layers):
             ps = L.qkv_ps is not None
-            if small or mid.get("qkv"):
+            if plan.qkv == FUSED:
                 q = ops.decode_qkv_rope(residual, L.qkv_ps if ps else L.qkv, eps, md.positions,
                                         md.slot_mapping, self.cos_sin, k_caches[li],
                                         v_caches[li], nq, nkv, preshuffled=ps, w_scale=L.qkv_s)
             else:
-                if fp8:
+                if plan.fp8_chain:
                     if pending is None:
                         xq, xs = ops.quant_rows_fp8(residual, ops.QUANT_NORM, L.input_norm, eps)
                     else:
                         xq, xs = ops.quant_rows_fp8(pending, ops.QUANT_ADDNORM, L.input_norm,
                                                     eps, residual)
-                    qkv = self._gemm8(xq, xs, L.qkv, L.qkv_s, dt, "qkv")
-                elif self._pg(T, L.qkv, proj="qkv"):
-                    qkv = ops.prefill_gemm(ops.rms_norm(residual, L.input_norm, eps), L.qkv)
+                    qkv = self._gemm8(plan.qkv, xq, xs, L.qkv, L.qkv_s, dt)
                 else:
-                    qkv = self._proj(ops.rms_norm(residual, L.input_norm, eps), L.qkv, L.qkv_s)
+                    x = ops.rms_norm(residual, L.input_norm, eps)
+                    qkv = ops.prefill_gemm(x, L.qkv) if plan.qkv == GEMM else ops.linear(x, L.qkv)
                 q = ops.rope_cache(qkv, md.positions, md.slot_mapping, self.cos_sin,
                                    k_caches[li], v_caches[li], nq, nkv, D)
             attn = torch.empty_like(q)
@@ -377,42 +357,35 @@ class LlamaModel:
                 ops.attention_prefill(q, k_caches[li], v_caches[li], md.block_tables,
                                       md.seq_kvlen, md.seq_qstart, md.tile_seq, md.tile_qoff,
                                       self.scale, out=attn)
-            if fp8 and not small:
+            if plan.fp8_chain:
                 aq, as_ = ops.quant_rows_fp8(attn.view(T, nq * D))
-                y = self._all_reduce(self._gemm8(aq, as_, L.o, L.o_s, dt, "o"))
+                y = self._all_reduce(self._gemm8(plan.o, aq, as_, L.o, L.o_s, dt))
                 xq, xs = ops.quant_rows_fp8(y, ops.QUANT_ADDNORM, L.post_norm, eps, residual)
-                if self._pg(T, xq, L.gate_up, mode=ops.GEMM_SILU, proj="gate_up"):
+                if plan.gate_up == GEMM:
                     # SiLU-mul fused into the gate_up GEMM epilogue: [T, I] out, plain quant
                     act = ops.prefill_gemm(xq, L.gate_up, ops.GEMM_SILU, xs=xs, ws=L.gate_up_s)
                     aq, as_ = ops.quant_rows_fp8(act)
                 else:
                     gu = ops.gemm_fp8(xq, xs, L.gate_up, L.gate_up_s, dt)
                     aq, as_ = ops.quant_rows_fp8(gu, ops.QUANT_SILU)
-                pending = self._all_reduce(self._gemm8(aq, as_, L.down, L.down_s, dt, "down"))
+                pending = self._all_reduce(self._gemm8(plan.down, aq, as_, L.down, L.down_s, dt))
                 continue
-            if small or mid.get("o"):
-                self._row_parallel(attn.view(T, nq * D), L, "o", residual)
-            else:
-                self._proj_residual(attn.view(T, nq * D), L.o, L.o_s, residual, "o")
-            if small and fp8 and T > self._fp8_gate_up_max():
-                # fp8 gate_up past its crossover: the library fp8 GEMM on row-quantised
-                # activations (norm fused into the quantiser), bf16 SiLU-mul for the fused down
-                xq, xs = ops.quant_rows_fp8(residual, ops.QUANT_NORM, L.post_norm, eps)
-                a = ops.silu_and_mul(self._gemm8(xq, xs, L.gate_up, L.gate_up_s, dt, "gate_up"))
-            elif small or mid.get("gate_up"):
+            self._proj_residual(plan.o, attn.view(T, nq * D), L, "o", residual)
+            if plan.gate_up == FUSED:
                 a = ops.decode_gate_up_silu(residual, L.gate_up_ps if ps else L.gate_up, eps,
                                             preshuffled=ps, w_scale=L.gate_up_s)
+            elif L.gate_up_s is not None:
+                # fp8 gate_up of a fused step past its crossover: an fp8 GEMM on row-quantised
+                # activations (norm fused into the quantiser), bf16 SiLU-mul for the fused down
+                xq, xs = ops.quant_rows_fp8(residual, ops.QUANT_NORM, L.post_norm, eps)
+                a = ops.silu_and_mul(self._gemm8(plan.gate_up, xq, xs, L.gate_up, L.gate_up_s, dt))
             else:
                 x = ops.rms_norm(residual, L.post_norm, eps)
-                if self._pg(T, L.gate_up, mode=ops.GEMM_SILU, proj="gate_up"):
+                if plan.gate_up == GEMM:
                     a = ops.prefill_gemm(x, L.gate_up, ops.GEMM_SILU)
                 else:
-                    gu = self._proj(x, L.gate_up, L.gate_up_s)
-                    a = ops.silu_and_mul(gu)
-            if small or mid.get("down"):
-                self._row_parallel(a, L, "down", residual)
-            else:
-                self._proj_residual(a, L.down, L.down_s, residual, "down")
+                    a = ops.silu_and_mul(ops.linear(x, L.gate_up))
+            self._proj_residual(plan.down, a, L, "down", residual)
         if rows is not None:
             residual = residual.index_select(0, rows)
             pending = None if pending is None else pending.index_select(0, rows)
@@ -420,149 +393,83 @@ class LlamaModel:
             return ops.fused_add_rms_norm(pending, residual, self.norm, eps)
         return ops.rms_norm(residual, self.norm, eps)
 
-    # "auto" routing of the prefill projections: (weight dtype, mode) -> the smallest row count
-    # from which the hand-written GEMM beat hipBLASLt in the cold-weight A/B on the 8B shapes.
-    # Round 4 re-measured against the library as the engine now runs it
-    # (profiles/r4_prefill_gemm_largem_ab.txt): bf16 on the tuned table (gemm_tuning) wins every
-    # projection at 2048-4096 rows (the hand-written gate_up+SiLU 0.84-0.88x), so bf16 routes
-    # here only when no tuned table is loaded (round 3: 1.06-1.10x over the untuned heuristic at
-    # 2600); fp8 gate_up+SiLU 1.08x at 3200, parity at 2048, 0.82-0.92x below; fp8 down
-    # 0.89-0.93x (was routed from 2048 in round 3).
-    # Against the shipped tuned tables the hand-written prefill GEMM wins nowhere that the
-    # workload reaches (round 5, profiles/r5_prefill_gemm_vs_tuned.txt: fp8 gate_up+SiLU
-    # 0.88-0.95x at 2560-3200 rows, bf16 down split-K 0.59-1.03x at 448-1152), so with a table
-    # loaded nothing is routed to it; without one (models with no shipped table) it keeps the
-    # shapes where it beat the untuned library (r3 / r4)
-    _PG_AUTO: dict = {}
-    _PG_AUTO_UNTUNED = {(torch.bfloat16, "gate_up"): 2048, (torch.uint8, "gate_up"): 2560}
+    # the measured routing tables (step_plan.py); read at call time, so an instance may
+    # assign its own
+    MIDM_ROUTES = sp.MIDM_ROUTES
+    MIDM_FP8_ROWS = sp.MIDM_FP8_ROWS
+    FP8_GATE_UP_WIDE_MAX = sp.FP8_GATE_UP_WIDE_MAX
+    FP8_FUSED_MAX_ROWS = sp.FP8_FUSED_MAX_ROWS
+    _PG_AUTO = sp.PG_AUTO
+    _PG_AUTO_UNTUNED = sp.PG_AUTO_UNTUNED
+    _PG_SPLITK = sp.PG_SPLITK
     gemm_tuned = False  # set by the model runner when a tuned library table is loaded
-    # row ranges where the split-K schedule (co-resident K slices of the few 256 x 256 tiles,
-    # parallel reduction) beat the UNTUNED hipBLASLt: bf16 down+residual 1.12-1.15x at M 512 /
-    # 1024, parity at 400 (profiles/r3_prefill_gemm_ab_bf16_splitk.txt); not used with a table
-    _PG_SPLITK = {(torch.bfloat16, "down"): (448, 1152)}
 
-    def _pg_splitk(self, T: int, w: torch.Tensor, proj: str) -> bool:
-        if (self.prefill_gemm != "auto" or self.device.type != "cuda" or self.tp_size > 1
-                or self.gemm_tuned):
-            return False
-        lo, hi = self._PG_SPLITK.get((w.dtype, proj), (1, 0))
-        return lo <= T <= hi
+    def step_plan(self, T: int) -> sp.StepPlan:
+        """The backend of each projection of a T-row prefill / mixed step, whether it runs the
+        activation-quantised fp8 chain and whether the runner pads its rows (step_plan.py).
+        Every fact is read now: tests and tuning tools assign them after construction."""
+        gpu = self.device.type == "cuda"
+        return sp.step_plan(T, sp.StepFacts(
+            gpu=gpu, quant=self.quant,
+            wdtype=torch.uint8 if gpu and self.quant == "fp8" else self.dtype,
+            tp_size=self.tp_size,
+            preshuffled=bool(self.layers) and self.layers[0].qkv_ps is not None,
+            hidden=self.cfg.hidden_size, q_width=self.n_heads * self.head_dim,
+            kv_width=self.n_kv_heads * self.head_dim, inter=self.inter,
+            gemm_tuned=self.gemm_tuned, prefill_gemm=self.prefill_gemm,
+            prefill_gemm_min_rows=self.prefill_gemm_min_rows,
+            small_prefill_fused=self.small_prefill_fused, fused_decode=self.fused_decode,
+            midm_routes=self.MIDM_ROUTES, pg_auto=self._PG_AUTO,
+            pg_auto_untuned=self._PG_AUTO_UNTUNED, pg_splitk=self._PG_SPLITK,
+            midm_fp8_rows=self.MIDM_FP8_ROWS, fp8_gate_up_wide_max=self.FP8_GATE_UP_WIDE_MAX,
+            fp8_fused_max_rows=self.FP8_FUSED_MAX_ROWS))
 
-    def _pg(self, T: int, *ops_, mode: int = 0, proj: str = "") -> bool:
-        """Route this prefill projection to the hand-written CDNA4 GEMM (ops.prefill_gemm):
-        ``prefill_gemm == "atta"`` (from ``prefill_gemm_min_rows`` rows) or ``"auto"`` (the
-        measured winners, _PG_AUTO), for shapes it takes.  Called as _pg(T, w) for bf16
-        (activation shape implied) or _pg(T, xq, w, mode)."""
-        if self.device.type != "cuda":
-            return False
-        w = ops_[-1]
-        if self.prefill_gemm == "auto":
-            m = self._PG_AUTO.get((w.dtype, proj))
-            if m is None and not self.gemm_tuned:
-                m = self._PG_AUTO_UNTUNED.get((w.dtype, proj))
-            if m is None or T < m:
-                return False
-        elif self.prefill_gemm != "atta" or T < self.prefill_gemm_min_rows:
-            return False
-        if len(ops_) == 1:
-            w = ops_[0]
-            x = torch.empty_strided((T, w.shape[1]), (w.shape[1], 1), dtype=w.dtype, device="meta")
-            return ops.prefill_gemm_ok(x, w, mode)
-        return ops.prefill_gemm_ok(ops_[0], ops_[1], mode)
-
-    def _gemm8(self, xq, xs, w, ws, dt, proj=""):
-        """fp8 prefill projection: the hand-written fp8 GEMM when routed there, else the
-        hipBLASLt row-scaled GEMM."""
-        if self._pg(xq.shape[0], xq, w, proj=proj):
+    @staticmethod
+    def _gemm8(backend, xq, xs, w, ws, dt):
+        """fp8 prefill projection on row-quantised activations: the hand-written fp8 GEMM or
+        the hipBLASLt row-scaled GEMM."""
+        if backend == GEMM:
             return ops.prefill_gemm(xq, w, xs=xs, ws=ws)
         return ops.gemm_fp8(xq, xs, w, ws, dt)
 
-    def _proj_residual(self, x, w, scale, residual, proj=""):
-        """residual += x @ w.T (row-parallel projection; TP: all-reduced partial sums)."""
-        if (scale is None and self._pg_splitk(x.shape[0], w, proj)
-                and ops.prefill_gemm_ok(x, w, ops.GEMM_RESADD)):
-            # split-K needs its T * S workgroups co-resident: TP = 1 only (one process per GPU)
+    def _proj_residual(self, backend, x, L, proj, residual):
+        """residual += x @ w.T (row-parallel o / down projection; TP: all-reduced partial
+        sums) on the plan's backend."""
+        if backend == FUSED:
+            return self._row_parallel(x, L, proj, residual)
+        w = getattr(L, proj)
+        if backend == GEMM_SPLITK:
             return ops.prefill_gemm(x, w, ops.GEMM_RESADD, residual=residual, schedule="splitk")
-        if scale is None and self._pg(x.shape[0], x, w, mode=ops.GEMM_RESADD, proj=proj):
-            if self.tp_size > 1:
-                return self.tp_group.all_reduce_residual(ops.prefill_gemm(x, w), residual)
-            return ops.prefill_gemm(x, w, ops.GEMM_RESADD, residual=residual)
         if self.tp_size > 1:
             # residual += sum over ranks, the add fused into the IPC reduction's epilogue
-            return self.tp_group.all_reduce_residual(self._proj(x, w, scale), residual)
-        return self._proj(x, w, scale, residual=residual)
-
-    # Per-projection row ranges where the mid-M kernel (fused epilogues included) beat the tuned
-    # library GEMM plus its separate norm / RoPE / SiLU kernels at the 8B shapes, cold weights,
-    # library rows padded to the tuning buckets as the engine runs them
-    # (profiles/r6_midm_vs_tuned.txt): qkv + RoPE 1.05-1.48x at 129-640 rows, down + residual
-    # 1.03-1.41x at 129-640, o + residual 1.05-1.17x at 129-188 and 1.06-1.12x at 448-640;
-    # gate_up + SiLU loses everywhere (0.59-0.93x: the kernel streams ~52 GB/s per CU at ~35 %
-    # MFMA, the library's 256-wide tiles run ~41 %).
-    MIDM_ROUTES = {"qkv": ((129, 640),), "o": ((129, 188), (448, 640)), "gate_up": (),
-                   "down": ((129, 640),)}
+            y = ops.prefill_gemm(x, w) if backend == GEMM else ops.linear(x, w)
+            return self.tp_group.all_reduce_residual(y, residual)
+        if backend == GEMM:
+            return ops.prefill_gemm(x, w, ops.GEMM_RESADD, residual=residual)
+        return ops.linear(x, w, residual=residual)
 
     def midm_route(self, T: int) -> dict:
-        """{projection: True} for the projections of a T-row step that run the mid-M kernel
-        (empty when the step cannot: TP, fp8, no pre-shuffled weights, rows past
+        """{projection: True} for the projections of a T-row 16-bit step that run the mid-M
+        kernel (empty when the step cannot: TP, fp8, no pre-shuffled weights, rows past
         ops.MIDM_MAX_M)."""
-        if (T <= ops.WIDE_ROWS or self.quant == "fp8" or self.tp_size != 1
-                or not self.fused_decode or not self.small_prefill_fused
-                or not self.proj_fusable(T)):
+        if T <= ops.WIDE_ROWS or self.quant == "fp8":
             return {}
-        return {p: any(lo <= T <= hi for lo, hi in r) for p, r in self.MIDM_ROUTES.items()}
-
-    # fp8 (weight-only) steps of these rows run the whole layer on the mid-M kernel's W8
-    # builds instead of the row-quantised library fp8 GEMMs (ATTA_MIDM_FP8_ROWS="lo-hi").  Off
-    # by default: the library's fp8 MFMA GEMMs win from 274 rows on at the 8B shapes (bench
-    # fp8 uncached planning 274 rows 5.68 vs 7.47 ms, burst 392 rows 6.42 vs 9.35 ms,
-    # profiles/r6_midm_fp8_negative.txt) - the W8 builds run bf16 MFMAs at ~35 % busy
-    _fp8_rows = os.environ.get("ATTA_MIDM_FP8_ROWS", "0")
-    MIDM_FP8_ROWS = ((0, -1) if _fp8_rows in ("", "0") else
-                     tuple(int(v) for v in _fp8_rows.split("-")))
-
-    # fp8 weights, TP = 1: most rows of a fused-path step whose gate_up + SiLU still runs the
-    # wide kernel's W8 build, by hidden size; past it the library fp8 GEMM wins (cold weights,
-    # bench_wide --fp8 --tuned, profiles/r6_wide_fp8.txt: 8B 38.4 vs 47.4 us at 75 rows, 50.9
-    # vs 47.4 at 128; 70B 106 vs 117 at 33 rows, 123 vs 118 at 64).  qkv / o / down keep the
-    # W8 builds to 128 rows (1.14-1.9x at <= 96 rows, 0.93-0.97x at 128 on the 70B shapes)
-    FP8_GATE_UP_WIDE_MAX = {4096: 112, 8192: 48}
-    # and the whole fused step: 70B fp8 prefill 33 / 76 / 112 / 128 rows 15.4 / 21.4 / 23.8 /
-    # 24.3 ms fused vs 20.6 / 22.4 / 23.2 / 23.3 on the library chain
-    # (profiles/r6_70b_fp8_planning_prefill.txt)
-    FP8_FUSED_MAX_ROWS = {8192: 96}
-
-    def _fp8_fused_max(self) -> int:
-        if self.tp_size > 1:
-            return ops.WIDE_ROWS
-        return self.FP8_FUSED_MAX_ROWS.get(self.cfg.hidden_size, ops.WIDE_ROWS)
-
-    def _fp8_gate_up_max(self) -> int:
-        if self.tp_size > 1:  # the TP shards' library GEMMs are launch-bound: not measured past it
-            return ops.WIDE_ROWS
-        return self.FP8_GATE_UP_WIDE_MAX.get(self.cfg.hidden_size, ops.WIDE_ROWS)
+        plan = self.step_plan(T)
+        return {p: True for p in sp.PROJS if getattr(plan, p) == FUSED}
 
     def midm_fp8_ok(self, T: int) -> bool:
-        """Does an fp8 step past the wide kernel's rows run every projection on the mid-M W8
-        builds?"""
-        lo, hi = self.MIDM_FP8_ROWS
-        return (self.quant == "fp8" and ops.WIDE_ROWS < T and lo <= T <= hi
-                and self.tp_size == 1 and self.fused_decode and self.small_prefill_fused
-                and self.proj_fusable(T))
+        """Does an fp8 step past the wide kernel's rows run qkv / o / down on the mid-M W8
+        builds (MIDM_FP8_ROWS)?  Its gate_up is past the fp8 crossover: the library fp8 GEMM."""
+        return self.quant == "fp8" and T > ops.WIDE_ROWS and self.step_plan(T).qkv == FUSED
 
     def small_prefill_ok(self, T: int) -> bool:
         """Does a (prefill or mixed) step of T rows run on the fused decode kernels - RMSNorm
         folded into the pre-shuffled skinny GEMVs, RoPE + KV write in the QKV epilogue, SiLU-mul
-        in gate_up?  The one predicate for forward() and the runner's row padding (ADVICE r4:
-        steps that take the library path are padded to its tuned buckets; fused_decode=False
-        turns the fused kernels off here too).  Up to 128 rows, 16-bit or fp8 weights, any TP
-        degree (the row-parallel sums go through _row_parallel); past 128 rows every
-        projection is routed on its own (midm_route)."""
-        if self.quant == "fp8":
-            if T > self._fp8_fused_max() or not (self.layers and self.layers[0].qkv_ps is not None):
-                return False
-        return (self.small_prefill_fused and self.fused_decode and T <= ops.WIDE_ROWS
-                and self.proj_fusable(T))
+        in gate_up?  Such steps stay unpadded; steps that take the library path are padded to
+        its tuned buckets (fused_decode=False turns the fused kernels off here too).
+        Up to 128 rows, 16-bit or fp8 weights, any TP degree (the row-parallel sums go through
+        _row_parallel); past 128 rows every projection is routed on its own (midm_route)."""
+        return not self.step_plan(T).pad_rows
 
     def proj_fusable(self, T: int) -> bool:
         """Can the layer projections of a T-row step run the hand-written weight-streaming
@@ -571,8 +478,7 @@ class LlamaModel:
         wide kernel's rows (past the fused push's rows the row-parallel sums take the IPC /
         RCCL all-reduce); the mid-M routes are measured at TP = 1 shapes only."""
         ps = bool(self.layers) and self.layers[0].qkv_ps is not None
-        return (self._proj_dims_ok and (self.tp_size == 1 or T <= ops.WIDE_ROWS)
-                and ops.fused_kernel(T, ps, ps and self.quant == "fp8") is not None)
+        return sp.proj_fusable(T, self._proj_dims_ok, self.tp_size, ps, self.quant)
 
     def decode_step_fusable(self, B: int) -> bool:
         """Can ``forward_decode`` run B sequences?  It runs every projection fused (gate_up

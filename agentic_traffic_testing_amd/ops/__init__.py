@@ -727,11 +727,17 @@ def prefill_gemm_ok(x: torch.Tensor, w: torch.Tensor, mode: int = GEMM_PLAIN) ->
     """Shapes the hand-written prefill GEMM (ops/csrc/prefill_gemm.hip) takes: bf16 or fp8
     (uint8 e4m3fn) operands, K a multiple of 64 bytes, output width a multiple of 256 (128
     for the SiLU mode), 16-B aligned rows."""
-    n = w.shape[0] // 2 if mode == GEMM_SILU else w.shape[0]
-    el = x.element_size()
-    return (x.dtype in (torch.bfloat16, torch.uint8) and w.dtype == x.dtype and x.dim() == 2
-            and x.shape[1] == w.shape[1] and (x.shape[1] * el) % 64 == 0 and x.stride(1) == 1
-            and (x.stride(0) * el) % 16 == 0 and w.is_contiguous()
+    return (w.dtype == x.dtype and x.dim() == 2 and x.shape[1] == w.shape[1]
+            and prefill_gemm_shape_ok(x.dtype, x.shape[1], w.shape[0], mode)
+            and x.stride(1) == 1 and (x.stride(0) * x.element_size()) % 16 == 0
+            and w.is_contiguous())
+
+
+def prefill_gemm_shape_ok(dtype: torch.dtype, k: int, w_rows: int, mode: int = GEMM_PLAIN) -> bool:
+    """The shape rule of ``prefill_gemm_ok`` for contiguous ``dtype`` operands x [M, k] and
+    w [w_rows, k], without the tensors (models/step_plan.py)."""
+    n = w_rows // 2 if mode == GEMM_SILU else w_rows
+    return (dtype in (torch.bfloat16, torch.uint8) and (k * dtype.itemsize) % 64 == 0
             and n % (128 if mode == GEMM_SILU else 256) == 0)
 
 

@@ -681,6 +681,62 @@ def test_midm_prefill_engine_matches_oracle(model):
 
 
 @pytest.mark.gpu
+def test_forward_runs_the_step_plan(monkeypatch):
+    """forward() runs each projection on the backend step_plan(T) names (models/step_plan.py):
+    17-, 150-, 400- and 700-token prompts, each prefilled in one step on bf16 weights with no
+    tuned table - all fused; the mid-M kernel for qkv / o / down; for qkv / down; the library
+    with split-K down.  Per step the fused qkv / gate_up kernels and the hand-written GEMM are
+    called num_layers times per projection the plan routes to them, and the tokens match the
+    fp32 dense oracle (near-tie rule)."""
+    from collections import Counter
+
+    from agentic_traffic_testing_amd import ops
+    vocab = 16000
+    cfg = EngineConfig(model="llama-8b-slice", device="cuda", max_model_len=1024,
+                       num_kv_blocks=512, max_num_batched_tokens=1024, max_num_seqs=8,
+                       graph_batch_sizes=(1, 2, 4, 8), prefill_gemm="auto")
+    eng = LLMEngine(cfg)
+    m = eng.runner.model
+    assert m.dtype == torch.bfloat16 and not m.gemm_tuned
+    steps, cur = {}, []  # rows of a forward() -> one Counter of op calls per forward()
+
+    for name in ("decode_qkv_rope", "decode_gate_up_silu", "prefill_gemm"):
+        def spy(*args, _name=name, _real=getattr(ops, name), **kw):
+            if cur:
+                cur[-1][_name + (":splitk" if kw.get("schedule") == "splitk" else "")] += 1
+            return _real(*args, **kw)
+
+        monkeypatch.setattr(ops, name, spy)
+    real_forward = m.forward
+
+    def forward(input_ids, *args, **kw):
+        cur.append(Counter())
+        steps.setdefault(input_ids.shape[0], []).append(cur[-1])
+        try:
+            return real_forward(input_ids, *args, **kw)
+        finally:
+            cur.pop()
+
+    monkeypatch.setattr(m, "forward", forward)
+    rng = np.random.default_rng(17)
+    nl = m.cfg.num_layers
+    for T, backends in ((17, "fused fused fused fused"), (150, "fused fused lib fused"),
+                        (400, "fused lib lib fused"), (700, "lib lib lib gemm_splitk")):
+        plan = m.step_plan(T)
+        assert [plan.qkv, plan.o, plan.gate_up, plan.down] == backends.split(), (T, plan)
+        outs, bad = _check(eng, [rng.integers(300, vocab, size=T).tolist()], n=5, tol_logit=0.25)
+        assert bad <= 1
+        assert len(steps[T]) == 1, (T, steps.keys())
+        names = backends.split()
+        assert steps[T][0] == Counter({k: v for k, v in {
+            "decode_qkv_rope": nl * (plan.qkv == "fused"),
+            "decode_gate_up_silu": nl * (plan.gate_up == "fused"),
+            "prefill_gemm": nl * names.count("gemm"),
+            "prefill_gemm:splitk": nl * names.count("gemm_splitk")}.items() if v}), (T, steps[T])
+    assert ops.prefill_gemm_error() == 0
+
+
+@pytest.mark.gpu
 def test_engine_starts_with_wide_kernel_off():
     """ATTA_WIDE_MAX_M=0 turns the wide / mid-M kernels off - the engine must start
     (no warm-up launch of a kernel the limits exclude) and serve a 48-row prefill on the
