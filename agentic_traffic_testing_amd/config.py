@@ -186,7 +186,8 @@ class EngineConfig:
     # Limit: the flash prefill kernel stages a sequence's whole block-table row in LDS (2048
     # entries = 32k tokens at block_size 16).  max_model_len beyond that sends EVERY prefill
     # to the slower v1 kernel (ops.prefill_impl picks by table width, not by the batch) -
-    # raise block_size with it (block_size 32 keeps flash up to 64k).
+    # raise block_size with it (block_size 32 keeps flash up to 64k).  The flash kernel takes
+    # block sizes 16, 32 and 64; larger pages need ATTA_PREFILL_IMPL=v1 (flash refuses them).
     max_model_len: int = 4096
     max_num_seqs: int = 12
     max_num_batched_tokens: int = 8192

@@ -227,6 +227,8 @@ PREFILL_IMPL = os.environ.get("ATTA_PREFILL_IMPL", "flash")
 # the flash kernel stages a sequence's whole block-table row in LDS (kBtLds entries: 32k
 # tokens at block size 16); wider tables take the v1 kernel
 FLASH_MAX_BT = 2048
+# ... and 64-key blocks at a fixed offset inside a page: pages of at most 64 keys
+FLASH_MAX_BLOCK_SIZE = 64
 # waves per flash-prefill workgroup (ops/csrc/flash_prefill.hip NW)
 FLASH_WAVES = int(os.environ.get("ATTA_FLASH_WAVES", "4"))
 if FLASH_WAVES not in (4, 8):  # the host tiles must match what the kernel covers
@@ -281,11 +283,15 @@ def attention_prefill(q, k_cache, v_cache, block_tables, seq_kvlen, seq_qstart, 
                                     seq_qstart, tile_seq, tile_qoff, q.shape[1],
                                     k_cache.shape[1], scale)
         return out
+    if k_cache.shape[2] > FLASH_MAX_BLOCK_SIZE:
+        raise ValueError(f"flash prefill takes KV block sizes 16 .. {FLASH_MAX_BLOCK_SIZE} "
+                         f"(got {k_cache.shape[2]}); use impl='v1' (ATTA_PREFILL_IMPL=v1)")
     pairs = tile_seq.shape[0] * k_cache.shape[1]
     ns = flash_kv_splits(pairs) if kv_splits is None else int(kv_splits)
     part = counters = None
     if ns > 1:
-        part = torch.empty(pairs * ns * 16640, dtype=torch.float32, device=q.device)
+        part = torch.empty(pairs * ns * flash_part_floats(), dtype=torch.float32,
+                           device=q.device)
         counters = _flash_counters(q.device, pairs)
     _native().flash_prefill(out, q, k_cache, v_cache, block_tables, seq_kvlen, seq_qstart,
                             tile_seq, tile_qoff, q.shape[1], k_cache.shape[1], scale, ns, part,
@@ -306,6 +312,12 @@ FLASH_KV_SPLITS = int(os.environ.get("ATTA_FLASH_KV_SPLITS", "0"))
 # fewest 64-key blocks per split (ATTA_FLASH_SPLIT_BLOCKS; a tile splits nblocks // this ways)
 FLASH_SPLIT_BLOCKS = int(os.environ.get("ATTA_FLASH_SPLIT_BLOCKS", "8"))
 _FLASH_COUNTERS: dict = {}
+
+
+def flash_part_floats() -> int:
+    """fp32 words of one split's partial: per workgroup column (32 per wave) 128 O values and
+    an (m, l) pair (ops/csrc/flash_prefill.hip part_bytes)."""
+    return FLASH_WAVES * 32 * (128 + 2)
 
 
 def flash_kv_splits(pairs: int) -> int:

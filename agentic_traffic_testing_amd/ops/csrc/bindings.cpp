@@ -181,9 +181,11 @@ void flash_prefill(at::Tensor out, const at::Tensor& q, const at::Tensor& k_cach
     TORCH_CHECK(part.has_value() && counters.has_value() &&
                     part->scalar_type() == at::kFloat && counters->scalar_type() == at::kInt &&
                     part->is_cuda() && counters->is_cuda() &&
-                    part->numel() * 4 >= tile_seq.size(0) * n_kv_heads * nsplit * 66560 &&
+                    part->numel() >= tile_seq.size(0) * n_kv_heads * nsplit *
+                                         static_cast<int64_t>(atta_flash_part_floats()) &&
                     counters->numel() >= tile_seq.size(0) * n_kv_heads,
-                "flash_prefill: split-KV needs fp32 partials [tiles * Hkv * nsplit * 16640] and "
+                "flash_prefill: split-KV needs fp32 partials [tiles * Hkv * nsplit * 16640 (4 "
+                "waves) / 33280 (8 waves)] and "
                 "zeroed int32 counters [tiles * Hkv]");
     part_p = part->data_ptr<float>();
     counters_p = counters->data_ptr<int>();

@@ -87,12 +87,14 @@ struct FlashParams {
   // publish (O, m, l) partials; the last to arrive merges them (device-scope hand-over)
   int nsplit;
   int split_blocks;  // key blocks per split at least (atta_set_flash_split_blocks)
-  float* part;    // [tile, Hkv, nsplit] slots of kPartBytes
+  float* part;    // [tile, Hkv, nsplit] slots of part_bytes(NW)
   int* counters;  // [tile * Hkv], zero between launches (the last arriver re-arms)
 };
-// one split's partial: 128 columns x 128 fp32 O values, then 128 (m, l) pairs
-constexpr uint32_t kPartOBytes = 128 * kD * 4;
-constexpr uint32_t kPartBytes = kPartOBytes + 128 * 8;
+// one split's partial: a workgroup's NW * 32 columns x 128 fp32 O values, then the columns'
+// (m, l) pairs.  (Sized for 128 columns whatever NW, the columns of waves 4-7 of an 8-wave
+// workgroup landed in the next split's slot and past the end of the buffer.)
+constexpr uint32_t part_o_bytes(int nw) { return static_cast<uint32_t>(nw) * 32 * kD * 4; }
+constexpr uint32_t part_bytes(int nw) { return part_o_bytes(nw) + static_cast<uint32_t>(nw) * 32 * 8; }
 constexpr int kMaxSplit = 8;
 constexpr int kSplitBlocks = 8;  // 512 keys: the default of split_blocks
 
@@ -191,8 +193,9 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void flash_prefill_kernel(FlashPar
   __syncthreads();  // lds_bt ready
 
   // ---- global -> register staging of one K/V block --------------------------------------
-  // Wave w stages keys 16 w .. 16 w + 15 of the block for BOTH tensors: with BS >= 16 those
-  // keys sit in one page, so the page lookup is wave-uniform (one LDS read + readfirstlane,
+  // Wave w stages keys 16 w .. 16 w + 15 of the block for BOTH tensors: with 16 <= BS <= 64
+  // those keys sit in one page at an offset that is the same for every block (the launcher
+  // rejects other block sizes), so the page lookup is wave-uniform (one LDS read + readfirstlane,
   // a scalar base) and every lane offset is a loop constant - the per-lane 64-bit address
   // arithmetic of 8 independent lookups was ~70 VALU per block and wave.
   //   K: lane l, chunk u -> key row 16 w + 4 u + (l >> 4), dims 8 (l & 15): each
@@ -400,6 +403,7 @@ __global__ __launch_bounds__(NW * 64, 8 / NW) void flash_prefill_kernel(FlashPar
     // ---- split-KV hand-over: publish (O, m, l) with device-scope stores, count arrivals; the
     // last workgroup of the tile merges every split's partial into its own registers
     __shared__ int fl_last;
+    constexpr uint32_t kPartOBytes = part_o_bytes(NW), kPartBytes = part_bytes(NW);
     const auto rw = dev_rsrc(p.part);
     const int pair = tile * p.n_kv_heads + hk;
     const uint32_t base = static_cast<uint32_t>(pair * p.nsplit) * kPartBytes;
@@ -513,6 +517,8 @@ static int launch(int G, dim3 grid, hipStream_t st, const FlashParams& p) {
 using namespace atta;
 
 void atta_set_flash_waves(int nw) { fp::g_flash_waves = nw == 8 ? 8 : 4; }
+// fp32 words of one (tile, KV head, split) partial slot at the current wave count
+int atta_flash_part_floats() { return static_cast<int>(fp::part_bytes(fp::g_flash_waves) / 4); }
 static int g_split_blocks = fp::kSplitBlocks;
 void atta_set_flash_split_blocks(int nb) { g_split_blocks = nb < 1 ? 1 : nb; }
 
@@ -526,6 +532,9 @@ int atta_flash_prefill(void* out, const void* q, const void* k_cache, const void
   int shift = 0;
   while ((1 << shift) < block_size) ++shift;
   if (head_dim != fp::kD || (1 << shift) != block_size || block_size < 16) return -1;
+  // a wave's 16 staged keys sit at ONE offset inside their page for every 64-key block
+  // (w_keyoff, a loop constant): true while a page holds at most one block
+  if (block_size > fp::kKB) return -1;
   if (n_q_heads % n_kv_heads || G > 8 || ((G & (G - 1)) && G != 3)) return -1;
   // 16-byte row loads of q / stores of out need 8-element aligned row strides
   if (q_stride % 8 || out_stride % 4) return -1;
@@ -551,7 +560,9 @@ int atta_flash_prefill(void* out, const void* q, const void* k_cache, const void
   if (nsplit < 1 || nsplit > fp::kMaxSplit) return -1;
   if (nsplit > 1 && (part == nullptr || counters == nullptr)) return -2;
   // 32-bit byte offsets of the device-scope partial stores
-  if (static_cast<int64_t>(num_tiles) * n_kv_heads * nsplit * fp::kPartBytes > 0x7FFFFFFF) return -1;
+  if (static_cast<int64_t>(num_tiles) * n_kv_heads * nsplit * fp::part_bytes(fp::g_flash_waves) >
+      0x7FFFFFFF)
+    return -1;
   prm.nsplit = nsplit;
   prm.split_blocks = g_split_blocks;
   prm.part = part;

@@ -159,4 +159,5 @@ void atta_set_splitk_half(int on);
 void atta_set_flash_split_blocks(int nb);
 int atta_midm_plan(int M, int ntiles, int K, int epi, int64_t ws_floats, int* bmt, int* ksplit);
 void atta_set_flash_waves(int nw);
+int atta_flash_part_floats();
 int atta_prefill_gemm_config(int schedule, int group_m, int ablate);

@@ -1,4 +1,11 @@
-"""Shared test helpers: an independent dense (unpaged) Llama forward used as the oracle."""
+"""Shared test helpers: an independent dense (unpaged) Llama forward used as the oracle, and
+builders of paged-attention inputs whose outputs are known in closed form."""
+import functools
+import math
+import os
+from dataclasses import dataclass, field
+
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -113,3 +120,360 @@ def greedy_reference_fp8(model, prompt, n):
         out.append(t)
         ids.append(t)
     return out
+
+
+# =========================================================================================
+# Paged-attention inputs whose outputs are known in closed form (test_attention_exact.py).
+#
+# Census: Q = 0, so every visible key weighs the same, and V is one-hot per key: a query at
+# position pos must return (visible keys per dim) / (pos + 1) - integer counts over an
+# integer, exact in the kernels' fp32 accumulators and rounded once to the output type.
+# Needle: K rows are random +-1 vectors u_j and every (query token, head) asks for one
+# visible key t with q = NEEDLE_A * u_t: that key's score beats every other by tens of nats,
+# so the output must be V[t], and the V rows of a sequence are pairwise distinct.
+# All values are small integers (V of the needle: eighths), exact in bf16 and fp16; the
+# builders keep them as int8 on the CPU and the tests cast them to the type under test.
+# =========================================================================================
+ATT_D = 128
+ATT_HKV = 2                      # two KV heads: the KV-head index must matter
+ATT_GROUPS = (1, 2, 3, 4, 8)     # GQA group sizes every launcher instantiates
+ATT_SCALE = 1 / math.sqrt(ATT_D)
+NEEDLE_A = 8                     # q = NEEDLE_A * u_t: 1024 * scale = 90.5 nats on the target
+NEEDLE_OFF_MASS = 2.0 ** -20     # most softmax mass a needle row may leave off its target
+NEEDLE_ATOL = 2.0 ** -16
+
+PREFILL_FULL = [(n, n) for n in (1, 15, 16, 17, 63, 64, 65, 127, 128, 129, 200)]
+PREFILL_CHUNKS = [(c + q, q) for c in (1, 15, 16, 63, 64, 65, 100) for q in (1, 2, 33, 130)]
+PREFILL_SEQS = PREFILL_FULL + PREFILL_CHUNKS
+SPLIT_SEQS = [(64 * b + r, 17) for b in (1, 2, 3, 7, 8, 9) for r in (0, 1, 63)]
+
+
+def attn_rtol(dtype) -> float:
+    """Relative tolerance: the one rounding to the output type moves a value by at most
+    2^-8 (bf16: 8 significand bits) / 2^-11 (fp16: 11) of itself; the kernels' fp32
+    normalisation and merge arithmetic add around 1e-6."""
+    return 2.0 ** -8 if dtype == torch.bfloat16 else 2.0 ** -11
+
+
+def census_dim(j, code: str, hk: int = 0):
+    """Dim that key j of KV head hk sets.  Code A walks the dims key by key; code B names the
+    key's 16-key tile (and its 2048-key span), so a dropped key and a key read from the wrong
+    place in its tile show up in different codes."""
+    j = np.asarray(j, dtype=np.int64)
+    if code == "A":
+        base = j % ATT_D
+    elif code == "B":
+        base = ((j // 16) * 5 + j // 2048) % ATT_D
+    else:
+        raise ValueError(code)
+    return (base + 37 * hk) % ATT_D
+
+
+@functools.lru_cache(maxsize=None)
+def census_drop_margin(n: int, code: str) -> float:
+    """For a row that sees keys [0, n): over every visible key, the largest relative change of
+    an output element when that key is deleted from the closed-form answer; the smallest of
+    these over the keys.  (inf for n = 1: no answer is left.)  Code B alone is blind inside a
+    tile (its 16 keys set one dim), so the tests take the larger margin of the two codes -
+    both run on every shape."""
+    if n < 2:
+        return math.inf
+    c = np.bincount(census_dim(np.arange(n), code), minlength=ATT_D).astype(np.float64)
+    exp = c / n
+    worst = math.inf
+    for d in np.nonzero(c)[0]:  # every key of dim d changes the answer the same way
+        alt = c.copy()
+        alt[d] -= 1
+        alt /= n - 1
+        nz = exp > 0
+        worst = min(worst, float((np.abs(alt - exp)[nz] / exp[nz]).max()))
+    return worst
+
+
+def census_max_keys(dtype) -> int:
+    """Longest census sequence for this output type: past it some dim counts so many keys
+    that one key more or less moves it by under 4x the tolerance (both codes put n / 128 keys
+    on a dim, and a count c moves by about 1 / c: 1 / 64 = 4 * 2^-8 at 8192 keys, 1 / 512 =
+    4 * 2^-11 at 65536)."""
+    return 7936 if dtype == torch.bfloat16 else 65024
+
+
+def decode_waves(part_tokens: int) -> int:
+    """Waves per workgroup of attention_decode_v2's instantiation for this partition size."""
+    w128 = 8
+    try:
+        if int(os.environ.get("ATTA_ATTN128_WAVES", "8")) == 4:
+            w128 = 4
+    except ValueError:
+        pass
+    return {64: 4, 128: w128, 256: 8, 512: 16}[part_tokens]
+
+
+def decode_merge_trip(part_tokens: int, g: int) -> int:
+    """Partitions one trip of the last arriver's merge loop folds (attention_decode.hip: NG
+    merge groups of G * 16 threads, PPI partitions each)."""
+    ng = min(decode_waves(part_tokens) * 64 // (g * 16), 16)
+    return ng * (8 if ng <= 4 else 4)
+
+
+def decode_kvlens(part_tokens: int, g: int, max_keys: int = 65536):
+    """(kvlens, partitions of the grid) of one decode launch: every length up to a partition
+    and a tile more, lengths around partition edges (the grid's last partition among them),
+    one sequence whose merge takes a second trip (where 64 partitions and max_keys allow it)
+    and one kvlen = 0 dummy row."""
+    pt = part_tokens
+    trip = decode_merge_trip(pt, g)
+    long = trip * pt + 5 if trip + 1 <= 64 and trip * pt + 5 <= max_keys else None
+    parts = math.ceil(long / pt) if long else 5
+    ks = list(range(1, pt + 18))
+    for m in (2, 3):
+        ks += [m * pt - 1, m * pt, m * pt + 1]
+    ks += [(parts - 1) * pt + 1, parts * pt - 1, parts * pt]
+    if long:
+        ks.append(long)
+    ks = [k for k in ks if k <= max_keys]
+    return ks + [0], parts
+
+
+def prefill_tiles(seqs, tile: int):
+    ts, to = [], []
+    for i, (_, ql) in enumerate(seqs):
+        for off in range(0, ql, tile):
+            ts.append(i)
+            to.append(off)
+    return torch.tensor(ts, dtype=torch.int32), torch.tensor(to, dtype=torch.int32)
+
+
+@dataclass
+class AttnCase:
+    """One launch's inputs (CPU, int8) and its closed-form answer (fp64)."""
+    seqs: list                    # (kvlen, qlen); kvlen 0: a dummy row that owns one page
+    bs: int
+    g: int
+    k_cache: torch.Tensor         # [nb, Hkv, bs, D] int8
+    v_cache: torch.Tensor         # [nb, Hkv, D, bs] int8, times v_unit
+    v_unit: float
+    q: torch.Tensor               # [T, Hq, D] int8
+    block_tables: torch.Tensor    # [S, W] int32, garbage past each sequence's last page
+    seq_kvlen: torch.Tensor
+    seq_qstart: torch.Tensor
+    expected: torch.Tensor        # [T, Hq, D] fp64 (rows of dummy sequences: 0)
+    live_rows: torch.Tensor       # [T] bool: rows of sequences with keys
+    key_off: list                 # first row of each sequence in k_dense / v_dense
+    k_dense: torch.Tensor         # [N, Hkv, D] int8: each sequence's whole pages, key order
+    v_dense: torch.Tensor
+    targets: torch.Tensor | None = None   # needle: [T, Hq] key index
+    kinds: set = field(default_factory=set)  # needle: kinds of target some row asks for
+
+    def tensors(self, dtype, device):
+        """q, k_cache, v_cache in ``dtype`` and the int32 metadata, on ``device``."""
+        v = self.v_cache.to(torch.float32) * self.v_unit
+        return (self.q.to(dtype).to(device), self.k_cache.to(dtype).to(device),
+                v.to(dtype).to(device), self.block_tables.to(device),
+                self.seq_kvlen.to(device), self.seq_qstart.to(device))
+
+    def dense(self, i: int):
+        """fp64 K, V [alloc, Hkv, D] of sequence i: its kvlen keys, then the stale slots of its
+        last page."""
+        a, b = self.key_off[i], self.key_off[i + 1]
+        return self.k_dense[a:b].double(), self.v_dense[a:b].double() * self.v_unit
+
+    def rows(self, i: int):
+        return int(self.seq_qstart[i]), int(self.seq_qstart[i + 1])
+
+
+def _paged_layout(seqs, bs, seed, nb_extra=8):
+    """Pages in a random permutation, garbage table entries past each sequence's last page."""
+    gen = torch.Generator().manual_seed(seed)
+    nblk = [max(1, math.ceil(kv / bs)) for kv, _ in seqs]
+    nb = sum(nblk) + nb_extra
+    perm = torch.randperm(nb, generator=gen)
+    bt = torch.zeros(len(seqs), max(nblk) + 2, dtype=torch.int32)
+    o = 0
+    for i, n in enumerate(nblk):
+        bt[i, :n] = perm[o:o + n].to(torch.int32)
+        bt[i, n:] = -7 if i % 2 else 0  # must never be read
+        o += n
+    return bt, nb, nblk, np.random.default_rng(seed)
+
+
+def _randint8(rng, lo, hi, shape):
+    """int8 tensor of integers in [lo, hi]."""
+    return torch.from_numpy(rng.integers(lo, hi + 1, size=shape, dtype=np.int8))
+
+
+def _finish_case(seqs, bs, g, bt, nb, nblk, k_dense, v_dense, k_fill, v_fill, v_unit):
+    """Scatter the dense keys into the paged caches; stale slots keep the fill values."""
+    hkv = ATT_HKV
+    alloc = [n * bs for n in nblk]
+    key_off = [0] + list(np.cumsum(alloc))
+    seq_id = torch.repeat_interleave(torch.arange(len(seqs)), torch.tensor(alloc))
+    j = torch.arange(int(key_off[-1])) - torch.tensor(key_off[:-1])[seq_id]
+    page = bt[seq_id, j // bs].long()
+    off = j % bs
+    k_cache = k_fill(nb, hkv, bs, ATT_D)
+    v_cache = v_fill(nb, hkv, ATT_D, bs)
+    k_cache[page, :, off, :] = k_dense
+    v_cache[page, :, :, off] = v_dense
+    qlens = [q for _, q in seqs]
+    qstart = torch.tensor([0] + list(np.cumsum(qlens)), dtype=torch.int32)
+    live = torch.repeat_interleave(torch.tensor([kv > 0 for kv, _ in seqs]), torch.tensor(qlens))
+    T = int(qstart[-1])
+    return AttnCase(seqs=list(seqs), bs=bs, g=g, k_cache=k_cache, v_cache=v_cache, v_unit=v_unit,
+                    q=torch.zeros(T, hkv * g, ATT_D, dtype=torch.int8), block_tables=bt,
+                    seq_kvlen=torch.tensor([kv for kv, _ in seqs], dtype=torch.int32),
+                    seq_qstart=qstart, expected=torch.zeros(T, hkv * g, ATT_D, dtype=torch.float64),
+                    live_rows=live, key_off=[int(x) for x in key_off], k_dense=k_dense,
+                    v_dense=v_dense)
+
+
+def census_case(seqs, bs: int, g: int, code: str, seed: int = 0) -> AttnCase:
+    """Q = 0, K random, V one-hot by ``census_dim``; expected = visible keys per dim over the
+    number of visible keys.  Stale slots of a sequence's last page continue its code and every
+    other unowned slot holds V = 1 in all dims: a key read from past the end shows."""
+    bt, nb, nblk, rng = _paged_layout(seqs, bs, seed)
+    n_keys = sum(nblk) * bs
+    k_dense = _randint8(rng, -3, 3, (n_keys, ATT_HKV, ATT_D))
+    jj = np.concatenate([np.arange(n * bs) for n in nblk])
+    v_dense = torch.zeros(n_keys, ATT_HKV, ATT_D, dtype=torch.int8)
+    for hk in range(ATT_HKV):
+        v_dense[torch.arange(n_keys), hk, torch.from_numpy(census_dim(jj, code, hk))] = 1
+    case = _finish_case(
+        seqs, bs, g, bt, nb, nblk, k_dense, v_dense,
+        lambda *s: _randint8(rng, -3, 3, s),
+        lambda *s: torch.ones(s, dtype=torch.int8), 1.0)
+    for i, (kv, ql) in enumerate(seqs):
+        if kv == 0:
+            continue
+        r0, r1 = case.rows(i)
+        v = case.v_dense[case.key_off[i]:case.key_off[i] + kv].double()  # [kv, Hkv, D]
+        if ql == 1:
+            cnt = v.sum(0, keepdim=True)
+        else:
+            cnt = v.cumsum(0)[kv - ql:]
+        pos1 = torch.arange(kv - ql + 1, kv + 1, dtype=torch.float64)[:, None, None]
+        case.expected[r0:r1] = (cnt / pos1).repeat_interleave(g, dim=1)
+    return case
+
+
+def _needle_candidates(pos: int, edges, rng):
+    cands = [("first", 0), ("diag", pos), ("tile16", 16 * (pos // 16))]
+    for e in edges:
+        m = e * (pos // e)
+        if m >= 1:
+            cands += [("edge_last", m - 1), ("edge_first", m)]
+    cands.append(("random", int(rng.integers(0, pos + 1))))
+    seen, out = set(), []
+    for kind, t in cands:
+        if t not in seen:
+            seen.add(t)
+            out.append((kind, t))
+    return out
+
+
+def needle_case(seqs, bs: int, g: int, edges=(64,), seed: int = 0) -> AttnCase:
+    """K[j] = random +-1 vectors, q = NEEDLE_A * K[t] of the head's KV head, V rows multiples of
+    1/8 in [-2, 2] with key j's binary code as +-1 in dims 0..15 (pairwise distinct rows) and
+    the KV head's sign in dim 16; expected = V[t].  Row r's head c of a group asks for
+    candidate (r + c) of: key 0, the diagonal, the first key of the last 16-key tile, the last
+    key before and the first key at each multiple of ``edges`` (partitions, 64-key blocks), a
+    random key - so the heads of a group differ wherever the row sees G keys."""
+    bt, nb, nblk, rng = _paged_layout(seqs, bs, seed)
+    n_keys = sum(nblk) * bs
+    k_dense = _randint8(rng, 0, 1, (n_keys, ATT_HKV, ATT_D)) * 2 - 1
+    v_dense = _randint8(rng, -16, 16, (n_keys, ATT_HKV, ATT_D))
+    jj = torch.from_numpy(np.concatenate([np.arange(n * bs) for n in nblk]))
+    bits = ((jj[:, None] >> torch.arange(16)[None, :]) & 1).to(torch.int8) * 16 - 8
+    v_dense[:, :, :16] = bits[:, None, :]
+    for hk in range(ATT_HKV):
+        v_dense[:, hk, 16] = 8 if hk else -8
+    case = _finish_case(
+        seqs, bs, g, bt, nb, nblk, k_dense, v_dense,
+        lambda *s: _randint8(rng, 0, 1, s) * 2 - 1,
+        lambda *s: torch.full(s, 16, dtype=torch.int8), 0.125)
+    hq = ATT_HKV * g
+    case.targets = torch.zeros(case.q.shape[0], hq, dtype=torch.int64)
+    for i, (kv, ql) in enumerate(seqs):
+        if kv == 0:
+            continue
+        r0, _ = case.rows(i)
+        for t in range(ql):
+            pos = kv - ql + t
+            cands = _needle_candidates(pos, edges, rng)
+            have = {k for _, k in cands}
+            while len(cands) < min(g, pos + 1):  # enough distinct targets for the group
+                k = int(rng.integers(0, pos + 1))
+                if k not in have:
+                    have.add(k)
+                    cands.append(("random", k))
+            for h in range(hq):
+                kind, key = cands[(r0 + t + h % g + (h // g)) % len(cands)]
+                case.targets[r0 + t, h] = key
+                case.kinds.add(kind)
+        tg = case.targets[r0:r0 + ql] + case.key_off[i]          # [ql, Hq] dense rows
+        hk = (torch.arange(hq) // g)[None, :].expand_as(tg)
+        case.q[r0:r0 + ql] = case.k_dense[tg, hk] * NEEDLE_A
+        case.expected[r0:r0 + ql] = case.v_dense[tg, hk].double() * case.v_unit
+    return case
+
+
+def needle_off_mass(case: AttnCase, scale: float = ATT_SCALE) -> float:
+    """Largest softmax mass any row leaves off its target key, in fp64."""
+    worst = 0.0
+    g = case.g
+    for i, (kv, ql) in enumerate(case.seqs):
+        if kv == 0:
+            continue
+        r0, r1 = case.rows(i)
+        k = case.k_dense[case.key_off[i]:case.key_off[i] + kv].float()   # [kv, Hkv, D]
+        q = case.q[r0:r1].float()                                         # [ql, Hq, D]
+        pos = torch.arange(kv - ql, kv)
+        for hk in range(ATT_HKV):
+            qh = q[:, hk * g:(hk + 1) * g]                                # [ql, G, D]
+            s = torch.einsum("kd,qgd->qgk", k[:, hk], qh).double() * scale  # exact integers
+            tg = case.targets[r0:r1, hk * g:(hk + 1) * g]
+            s = s - s.gather(2, tg[..., None])
+            w = torch.exp(s)
+            w = w.masked_fill(torch.arange(kv)[None, None, :] > pos[:, None, None], 0.0)
+            w.scatter_(2, tg[..., None], 0.0)
+            worst = max(worst, float(w.sum(-1).max()))
+    return worst
+
+
+def dense_attention64(q, k, v, pos, scale, drop=None, shift: int = 0, swap=None):
+    """fp64 softmax attention of rows q [R, D] at positions pos [R] over one head's dense keys
+    k, v [n, D]: row r sees keys j <= pos[r] + shift.  The wrong variants the tests must
+    catch: ``drop`` hides one key, ``shift`` moves the causal limit, ``swap`` = (a, b)
+    exchanges two rows of V only."""
+    n = k.shape[0]
+    vis = torch.arange(n)[None, :] <= (pos[:, None] + shift)
+    if drop is not None:
+        vis[:, drop] = False
+    if swap is not None:
+        v = v.clone()
+        v[list(swap)] = v[list(swap[::-1])]
+    s = (q.double() @ k.double().t()) * scale
+    p = torch.softmax(s.masked_fill(~vis, float("-inf")), dim=-1)
+    return p @ v.double()
+
+
+def exact_errors(got, exp, rtol: float, atol: float = 0.0):
+    """(elements outside atol + rtol * |exp| - NaN counts, largest relative error over the
+    elements whose expectation is not 0)."""
+    got, exp = got.double().cpu(), exp.double().cpu()
+    err = (got - exp).abs()
+    bad = int((~(err <= atol + rtol * exp.abs())).sum())
+    nz = exp != 0
+    rel = float((err[nz] / exp[nz].abs()).max()) if bool(nz.any()) else 0.0
+    return bad, rel
+
+
+def assert_exact(got, exp, dtype, atol: float = 0.0, what: str = "") -> float:
+    """The sharp comparator: |got - exp| <= atol + attn_rtol(dtype) * |exp| everywhere.
+    Prints and returns the largest relative error."""
+    rtol = attn_rtol(dtype)
+    bad, rel = exact_errors(got, exp, rtol, atol)
+    print(f"EXACT {what} dtype={str(dtype).split('.')[-1]} max_rel_err={rel:.3e} "
+          f"rtol={rtol:.3e} atol={atol:.3e}")
+    assert bad == 0, f"{what}: {bad} elements off the closed-form answer, max rel err {rel:.4g}"
+    return rel
