@@ -276,6 +276,27 @@ class EngineConfig:
     # a TP worker that has not registered on the step channel this long after rank 0
     # created it is reported dead (covers workers that die while loading weights)
     tp_register_timeout_s: float = 900.0
+    # speculative decoding: "" = off, "ngram" = prompt-lookup drafts (the continuation of the
+    # most recent earlier occurrence of the last spec_ngram_max .. spec_ngram_min tokens)
+    # verified in one decode step of 1 + k rows per sequence.  Sampling is a pure function of
+    # (logits, seed, step, token id), so a draft is accepted iff it equals the sample of its
+    # row: outputs are plain decode's.  At most spec_tokens drafts per sequence and step,
+    # clipped to 16 // G - 1 (the multi-query decode kernel's columns).  Single GPU only.
+    speculative: str = ""
+    spec_tokens: int = 3
+    spec_ngram_max: int = 4
+    spec_ngram_min: int = 2
+
+    def __post_init__(self):
+        if self.speculative not in ("", "ngram"):
+            raise ValueError(f"speculative={self.speculative!r}: '' or 'ngram'")
+        if self.speculative:
+            if self.tensor_parallel_size > 1:
+                raise ValueError("speculative decoding runs on one GPU: tensor_parallel_size "
+                                 f"= {self.tensor_parallel_size} is not supported with it")
+            if self.spec_tokens < 1 or not 1 <= self.spec_ngram_min <= self.spec_ngram_max:
+                raise ValueError("speculative decoding needs spec_tokens >= 1 and "
+                                 "1 <= spec_ngram_min <= spec_ngram_max")
 
     def replace(self, **kw) -> "EngineConfig":
         return replace(self, **kw)
@@ -310,6 +331,11 @@ class EngineConfig:
         n = _env_int("LLM_TENSOR_PARALLEL_SIZE", 0)
         if n > 0:
             kw["tensor_parallel_size"] = n
+        if env.get("LLM_SPECULATIVE"):
+            kw["speculative"] = env["LLM_SPECULATIVE"]
+        n = _env_int("LLM_NUM_SPECULATIVE_TOKENS", 0)
+        if n > 0:
+            kw["spec_tokens"] = n
         if env.get("LLM_QUANTIZATION"):
             kw["quantization"] = env["LLM_QUANTIZATION"].strip().lower()
         kw.update({k: v for k, v in overrides.items() if v is not None})

@@ -19,6 +19,7 @@ from ..utils import roctx
 from .model_runner import ModelRunner
 from .scheduler import Batch, Scheduler
 from .sequence import SamplingParams, Sequence, SeqStatus
+from .spec_decode import Proposer, make_proposer
 from .tokenizer import get_tokenizer
 
 PENDING_TOKEN = -1  # output slot of a launched step whose token the host has not seen yet
@@ -95,6 +96,10 @@ class LLMEngine:
         # async look-ahead decode: the step launched but not yet collected (see step())
         self._inflight: _Inflight | None = None
         self._last_collect = 0.0
+        # speculative decoding (cfg.speculative): the draft proposer - settable, None = off -
+        # and its counters (verify steps run, draft tokens verified, drafts accepted)
+        self.proposer: Proposer | None = make_proposer(cfg)
+        self.spec_stats = {"verify_steps": 0, "draft_tokens": 0, "accepted_tokens": 0}
         # (a TP engine warms up itself once its worker group is fully set up)
         if cfg.startup_warmup and self.runner.is_cuda and not getattr(self, "_defer_warmup",
                                                                       False):
@@ -126,6 +131,17 @@ class LLMEngine:
                 self.generate([toks(n) for n in sizes], greedy)
         self.generate([toks(17)], SamplingParams(temperature=0.7, top_p=0.9, top_k=40,
                                                  max_tokens=2, ignore_eos=True, seed=1))
+        if self.proposer is not None and r.verify_rows() > 0:
+            # one verify step, so the multi-query attention's code object (and the fused
+            # kernels at its row count) load before the first request: drafts that repeat the
+            # last token, whatever the samples turn out to be
+            live, self.proposer = self.proposer, _RepeatProposer()
+            try:
+                self.generate([toks(17)] * 2, SamplingParams(temperature=0.0, max_tokens=6,
+                                                              ignore_eos=True))
+            finally:
+                self.proposer = live
+            self.spec_stats = {k: 0 for k in self.spec_stats}
         r.reset_state()
         self.total_steps = self.total_generated = self.total_prompt = 0
         self.batch_size_history = []
@@ -180,7 +196,15 @@ class LLMEngine:
                     return []
                 t0 = time.perf_counter()
                 self.timing["schedule"] += t0 - ts
-                if not (self.cfg.async_decode and self.runner.launchable(batch)):
+                if self.proposer is not None:
+                    # speculation on: no async look-ahead (it would need the token that
+                    # drafting needs); a step without drafts is a plain synchronous step
+                    drafts = self._drafts(batch)
+                    if drafts is not None:
+                        with roctx.range("engine.verify_step"):
+                            return self._verify_step(batch, drafts, t0)
+                if self.proposer is not None or not (self.cfg.async_decode
+                                                     and self.runner.launchable(batch)):
                     with roctx.range("engine.sync_step" if batch.num_decode == len(batch.seqs)
                                      else "engine.prefill_step"):
                         return self._sync_step(batch, t0)
@@ -284,6 +308,80 @@ class LLMEngine:
             self.timing["post"] += time.perf_counter() - now
             return outs
 
+    # -- speculative decoding -------------------------------------------------------------
+    def _drafts(self, batch) -> list | None:
+        """Draft tokens per sequence of a decode-only batch, or None when no sequence gets one
+        (the step is then a plain decode step).  Sequence i gets k_i <= min(spec_tokens,
+        16 // G - 1, max_tokens - n - 1, room to max_model_len) tokens of the proposer, none if
+        the KV pool cannot hold them (drafts never preempt); the step's rows are kept within
+        the runner's cap by trimming the longest draft, lowest batch index first."""
+        r = self.runner
+        S = len(batch.seqs)
+        cap = r.verify_rows()
+        if not (0 < S == batch.num_decode and S < cap) or any(n != 1 for n in batch.q_len):
+            return None
+        if r.is_cuda and r._special(batch):
+            return None  # a top-k / top-p row: the whole step samples through that kernel
+        max_kv = r.verify_max_kv(S)
+        if any(seq.num_tokens > max_kv for seq in batch.seqs):
+            return None
+        drafts = []
+        for seq in batch.seqs:
+            n = len(seq.output_ids)
+            k = min(r.spec_tokens, seq.sampling.max_tokens - n - 1,
+                    self.cfg.max_model_len - seq.num_tokens - 1, max_kv - seq.num_tokens)
+            d = list(self.proposer.propose(seq, k))[:k] if k > 0 else []
+            if d and not r.bm.ensure(seq.seq_id, seq.num_tokens + len(d)):
+                d = []
+            drafts.append([int(t) for t in d])
+        rows = S + sum(len(d) for d in drafts)
+        while rows > cap:
+            i = max(range(S), key=lambda j: (len(drafts[j]), -j))
+            drafts[i].pop()
+            rows -= 1
+        return drafts if any(drafts) else None
+
+    def _verify_step(self, batch, drafts: list, t0: float) -> list[RequestOutput]:
+        """Rows [o_{n-1}, d_1 .. d_k] give samples s_0 .. s_k; with a the largest value such
+        that d_i == s_{i-1} for all i <= a, the tokens s_0 .. s_a are what plain decode would
+        have produced: they are emitted in order, cut at the first stop.  The KV of rejected
+        rows is overwritten by later steps; the prefix cache sees accepted tokens only."""
+        with self.lock:
+            vb = Batch(seqs=list(batch.seqs), q_start=list(batch.q_start),
+                       q_len=[1 + len(d) for d in drafts], num_decode=len(batch.seqs))
+            samples = self.runner.verify(vb, drafts)
+            now = time.perf_counter()
+            self.timing["execute"] += now - t0
+            self.timing["steps"] += 1
+            st = self.spec_stats
+            st["verify_steps"] += 1
+            outs, n_new = [], 0
+            for seq, d, smp in zip(batch.seqs, drafts, samples):
+                a = 0
+                while a < len(d) and d[a] == int(smp[a]):
+                    a += 1
+                st["draft_tokens"] += len(d)
+                st["accepted_tokens"] += a
+                new, reason = [], None
+                for tok in smp[:a + 1]:
+                    tok = int(tok)
+                    seq.append(tok)
+                    seq.num_computed += 1
+                    new.append(tok)
+                    reason = self._stop_reason(seq, tok)
+                    if reason:
+                        break
+                if seq.first_token_time is None:
+                    seq.first_token_time = now
+                self.runner.bm.commit(seq.seq_id, seq.token_array(), seq.num_computed)
+                if reason:
+                    self.scheduler.finish(seq, reason)
+                outs.append(self._output(seq, new))
+                n_new += len(new)
+            self._account(vb, n_new, now - t0)
+            self.timing["post"] += time.perf_counter() - now
+            return outs
+
     def _stop_reason(self, seq: Sequence, tok: int, n_out: int | None = None) -> str | None:
         """``n_out``: output tokens up to and including ``tok`` (default: all of them)."""
         sp = seq.sampling
@@ -341,6 +439,13 @@ class LLMEngine:
 
     def est_max_concurrency(self) -> float:
         return self.runner.kv_total_tokens / max(1, self.cfg.max_model_len)
+
+
+class _RepeatProposer(Proposer):
+    """Warm-up drafts: the last token, k times."""
+
+    def propose(self, seq, k: int) -> list:
+        return [int(seq.token_array()[-1])] * k
 
 
 def token_array(ids) -> np.ndarray:

@@ -43,8 +43,11 @@ def _even(n: int) -> int:
 class MetaLayout:
     """int32-word layout of the packed per-step metadata buffer."""
 
-    def __init__(self, T: int, S: int, W: int, NT: int):
-        self.T, self.S, self.W, self.NT = T, S, W, NT
+    def __init__(self, T: int, S: int, W: int, NT: int, R: int | None = None):
+        # R: rows the sampler runs over - one per sequence, or every row of a verify step
+        # (speculative decoding), whose sampling fields are row-sized
+        R = S if R is None else R
+        self.T, self.S, self.W, self.NT, self.R = T, S, W, NT, R
         o = 0
         self.fields = {}
 
@@ -65,12 +68,12 @@ class MetaLayout:
         add("tile_seq", NT)
         add("tile_qoff", NT)
         add("feed_prev", 1)     # 1: decode rows take the previous step's device samples
-        add("temperature", S, torch.float32)
-        add("top_p", S, torch.float32)  # >= 1: off
-        add("top_k", S)                 # <= 0: off
-        add("logits_idx", S, torch.int64)
-        add("seeds", S, torch.int64)
-        add("steps", S, torch.int64)
+        add("temperature", R, torch.float32)
+        add("top_p", R, torch.float32)  # >= 1: off
+        add("top_k", R)                 # <= 0: off
+        add("logits_idx", R, torch.int64)
+        add("seeds", R, torch.int64)
+        add("steps", R, torch.int64)
         self.size = _even(o)
 
     def views(self, buf: torch.Tensor) -> dict:
@@ -165,7 +168,13 @@ class ModelRunner:
                 continue
             bk = sorted({p for p in cfg.graph_parts_buckets if p < mp} | {mp})
             self.part_tiers.append((mb, pt, mp, bk))
+        # drafts per sequence and verify step (speculative decoding; 0 = off)
+        self.spec_tokens = 0
+        if cfg.speculative and self.model.g in ops.MQ_GROUPS:
+            self.spec_tokens = max(0, min(cfg.spec_tokens, ops.mq_max_qlen(self.model.g) - 1))
         alloc_parts = max([self.max_parts] + [t[2] for t in self.part_tiers])
+        if self.spec_tokens and self.part_tokens not in ops.MQ_PART_TOKENS:
+            alloc_parts = max(alloc_parts, min(64, math.ceil(cfg.max_model_len / 256)))
         # decode graphs are captured per (batch bucket, partition bucket): the attention grid
         # is (seqs, kv heads, partitions) and every workgroup past a sequence's context still
         # costs a dispatch and a round trip - a 32-partition grid (max_model_len 8192) over
@@ -179,6 +188,15 @@ class ModelRunner:
         self.graph_sizes = [b for b in self.graph_sizes if b <= cap]
         self.max_seqs = max(cfg.max_num_seqs, self.graph_sizes[-1] if self.graph_sizes else 1)
         self.max_tokens = cfg.max_num_batched_tokens + self.max_seqs
+        # speculative decoding: a verify step carries 1 + k rows per sequence through the fused
+        # decode path, k <= 16 // G - 1 (the multi-query attention kernel's columns); its
+        # attention needs a partition shape that kernel has (64, 128, 256 tokens) - a batch
+        # whose tier has none verifies at 256, and contexts past 64 such partitions get no
+        # drafts.  ws_rows sizes the fused workspaces (q / attn / act / keys / tokens).
+        self.ws_rows = self.max_seqs
+        if self.spec_tokens:
+            self.ws_rows = max(self.max_seqs,
+                               min(self.max_seqs * (1 + self.spec_tokens), ops.WIDE_ROWS))
         if self.is_cuda and cfg.gemm_tuning:  # room for prefill row padding (tuning buckets)
             from ..tuning import bucket_rows
 
@@ -187,7 +205,7 @@ class ModelRunner:
         self.bm = BlockManager(self.num_blocks, self.block_size, cfg.enable_prefix_caching)
         # metadata buffers (max layout)
         self.max_layout = MetaLayout(self.max_tokens, self.max_seqs, self.bt_width,
-                                     self.max_tokens)
+                                     self.max_tokens, max(self.max_seqs, self.ws_rows))
         pin = self.is_cuda
         # two pinned metadata buffers, used alternately: a step's H2D copy may still be queued
         # while the host packs the next step (async look-ahead decode, TP workers); an event
@@ -199,7 +217,7 @@ class ModelRunner:
         self._h2d_done = [torch.cuda.Event() if self.is_cuda else None for _ in range(2)]
         self.meta_dev = torch.zeros(self.max_layout.size, dtype=torch.int32, device=self.device)
         # sampled tokens of in-flight steps land here (D2H, one slot per in-flight step)
-        self.tok_host = [torch.zeros(max(cfg.max_num_seqs, 256), dtype=torch.int64,
+        self.tok_host = [torch.zeros(max(cfg.max_num_seqs, self.ws_rows, 256), dtype=torch.int64,
                                      pin_memory=pin) for _ in range(2)]
         self._tok_done = [torch.cuda.Event() if self.is_cuda else None for _ in range(2)]
         # the prefill GEMM's error word as of the last prefill step (0: every wait succeeded)
@@ -221,12 +239,12 @@ class ModelRunner:
         H = self.mcfg.hidden_size
         dt, dev = self.dtype, self.device
         self.ws = {
-            "q": torch.empty(self.max_seqs, self.model.n_heads, 128, dtype=dt, device=dev),
-            "attn": torch.empty(self.max_seqs, self.model.n_heads, 128, dtype=dt, device=dev),
-            "act": torch.empty(self.max_seqs, self.model.inter, dtype=dt, device=dev),
-            "keys": torch.zeros(self.max_seqs * (self.model.vocab_shard // 16 + 1),
+            "q": torch.empty(self.ws_rows, self.model.n_heads, 128, dtype=dt, device=dev),
+            "attn": torch.empty(self.ws_rows, self.model.n_heads, 128, dtype=dt, device=dev),
+            "act": torch.empty(self.ws_rows, self.model.inter, dtype=dt, device=dev),
+            "keys": torch.zeros(self.ws_rows * (self.model.vocab_shard // 16 + 1),
                                 dtype=torch.int64, device=dev),
-            "tokens": torch.zeros(self.max_seqs, dtype=torch.int64, device=dev),
+            "tokens": torch.zeros(self.ws_rows, dtype=torch.int64, device=dev),
             "tp_keys": torch.zeros(self.max_seqs, dtype=torch.int64, device=dev),
             "counters": torch.zeros(self.max_seqs * nkv, dtype=torch.int32, device=dev),
             "part_out": self.part_out, "part_lse": self.part_lse,
@@ -243,7 +261,9 @@ class ModelRunner:
         self.graph_pool = None
         self.steps = 0
         self.graph_steps = 0
+        self.verify_steps = 0
         self.timing = {"graph_prep": 0.0, "graph_run": 0.0}
+        self._verify_rows: int | None = None
 
     def _room_for_decode_copies(self) -> bool:
         """The pre-shuffled decode copies double the 16-bit weights (16 GB for Llama-3.1-8B);
@@ -506,6 +526,105 @@ class ModelRunner:
                   "is shared or oversubscribed)", flush=True)
         return out
 
+    # -- speculative decoding: verify steps --------------------------------------------------
+    def verify_rows(self) -> int:
+        """Most rows (sequences + drafts) one verify step takes; 0: this runner cannot verify.
+        On the GPU that is the largest row count the fused decode step runs (<= 128 rows on
+        pre-shuffled 16-bit weights, <= 32 on fp8) inside the workspace; the CPU backend runs
+        verify steps through the reference ops."""
+        if self._verify_rows is None:
+            rows = 0
+            if self.spec_tokens > 0 and self.tp_size == 1:
+                rows = self.ws_rows
+                if self.is_cuda:
+                    ok = self.fused_decode and self.model.g in ops.MQ_GROUPS
+                    while ok and rows > 1 and not self.model.decode_step_fusable(rows):
+                        rows -= 1
+                    rows = rows if ok and rows > 1 else 0
+            self._verify_rows = rows
+        return self._verify_rows
+
+    def _verify_tier(self, batch_size: int) -> tuple:
+        """(partition tokens, partitions allocated) of a verify step of ``batch_size``
+        sequences: the decode tier of that batch size where the multi-query kernel has its
+        shape, else 256-token partitions."""
+        pt, mp, _ = self._tier(batch_size)
+        if pt not in ops.MQ_PART_TOKENS:
+            pt = 256
+            mp = min(64, max(1, math.ceil(self.cfg.max_model_len / pt)))
+        return pt, mp
+
+    def verify_max_kv(self, batch_size: int) -> int:
+        """Longest context (drafts included) a sequence of such a verify step may have."""
+        pt, mp = self._verify_tier(batch_size)
+        return pt * mp
+
+    def verify(self, batch: Batch, drafts: list) -> list:
+        """One verify step over a decode-only batch: sequence i's rows are its pending token
+        and ``drafts[i]`` (``batch.q_len[i] == 1 + len(drafts[i])``, KV room ensured by the
+        caller), every row is sampled with step = len(output_ids) + row.  Returns the samples
+        per sequence.  Runs eagerly (no graph, no look-ahead)."""
+        S = len(batch.seqs)
+        if not (0 < S == batch.num_decode and self.verify_rows() >= batch.num_tokens):
+            raise ValueError("verify() needs a decode-only batch within verify_rows()")
+        if self.is_cuda and self._special(batch):
+            raise ValueError("verify(): top-k / top-p rows take no drafts")
+        self.steps += 1
+        self.verify_steps += 1
+        ids, qs, ql = batch.arrays()
+        d = self.bm.build_batch(ids, qs, ql, self.bt_width, 0, S, 0, 0)
+        T = d["positions"].shape[0]
+        lay = MetaLayout(T, S, self.bt_width, 0, T)
+        input_ids = np.zeros(T, dtype=np.int32)
+        temps = np.zeros(T, dtype=np.float32)
+        seeds = np.zeros(T, dtype=np.int64)
+        steps = np.zeros(T, dtype=np.int64)
+        row = 0
+        for seq, s0, n, dr in zip(batch.seqs, batch.q_start, batch.q_len, drafts):
+            assert n == 1 + len(dr) and s0 == seq.num_tokens - 1
+            input_ids[row] = seq.token_array()[s0]
+            input_ids[row + 1:row + n] = dr
+            temps[row:row + n] = seq.sampling.temperature
+            seeds[row:row + n] = seq.seed
+            steps[row:row + n] = len(seq.output_ids) + np.arange(n)
+            row += n
+        arrays = dict(d)
+        arrays.update(input_ids=input_ids, temperature=temps, top_p=np.ones(T, dtype=np.float32),
+                      top_k=np.zeros(T, dtype=np.int32), seeds=seeds, steps=steps,
+                      logits_idx=np.arange(T, dtype=np.int64),
+                      feed_prev=np.zeros(1, dtype=np.int32))
+        pt, mp = self._verify_tier(S)
+        num_parts = max(1, math.ceil(int(arrays["seq_kvlen"].max()) / pt))
+        if num_parts > mp:
+            raise ValueError("verify(): context past verify_max_kv()")
+        host = self._pack(lay, arrays)
+        # header word 11: longest qlen | shortest qlen << 8 of a verify step (0: a plain step)
+        hdr = np.array([OP_STEP, lay.T, lay.S, lay.W, 0, S, num_parts, 0, 0, S, lay.size,
+                        int(max(batch.q_len)) | int(min(batch.q_len)) << 8], dtype=np.int32)
+        toks = self._run(hdr)[:T].cpu().numpy()
+        out, row = [], 0
+        for n in batch.q_len:
+            out.append(toks[row:row + n])
+            row += n
+        return out
+
+    def _forward_verify(self, v: dict, md: AttnMeta, num_parts: int, max_qlen: int,
+                        min_qlen: int):
+        m = self.model
+        T = v["input_ids"].shape[0]
+        if self.is_cuda:
+            # the fused decode step or nothing: no fall-back to another path on the GPU
+            if not (self.fused_decode and m.decode_step_fusable(T)):
+                raise RuntimeError(f"verify step of {T} rows: fused decode path unavailable")
+            pt, _ = self._verify_tier(md.num_decode)
+            ws = {**self.ws, "part_tokens": pt, "max_parts": num_parts}
+            return m.forward_decode(v["input_ids"], md, self.k_layers, self.v_layers, ws,
+                                    v["temperature"], v["seeds"], v["steps"], max_qlen=max_qlen,
+                                    min_qlen=min_qlen)
+        hidden = m.forward(v["input_ids"], md, self.k_layers, self.v_layers, self.part_out,
+                           self.part_lse, num_parts, self.part_tokens)
+        return ops.sample(m.compute_logits(hidden), v["temperature"], v["seeds"], v["steps"])
+
     def take_kernel_error(self) -> int:
         """Error words seen since the previous call (the /health check), then cleared."""
         with self._kernel_error_lock:
@@ -577,6 +696,13 @@ class ModelRunner:
     def _run(self, hdr):
         """Execute one step from its header; the packed metadata is in ``meta_host``."""
         T, S, W, NT, num_decode, num_parts, bucket, special, n, size = (int(x) for x in hdr[1:11])
+        if int(hdr[11]):  # verify step: row-sized sampling fields, multi-query attention
+            lay = MetaLayout(T, S, W, NT, T)
+            dev = self.meta_dev[:size]
+            self._h2d(dev, size)
+            v = lay.views(dev)
+            return self._forward_verify(v, self._meta(v, num_decode, NT), num_parts,
+                                        int(hdr[11]) & 0xFF, int(hdr[11]) >> 8)
         if bucket:
             key = (bucket, num_parts, special)
             io = self.graph_io[key]

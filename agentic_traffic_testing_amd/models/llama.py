@@ -496,8 +496,15 @@ class LlamaModel:
 
     def forward_decode(self, input_ids: torch.Tensor, md: AttnMeta, k_caches, v_caches, ws: dict,
                        temperature, seeds, steps, prev_tokens=None,
-                       feed_prev=None, top_p=None, top_k=None) -> torch.Tensor:
-        """Fused decode step (every sequence has one query token); returns sampled ids.
+                       feed_prev=None, top_p=None, top_k=None, max_qlen: int = 1,
+                       min_qlen: int = 1) -> torch.Tensor:
+        """Fused decode step; returns sampled ids, one per row.  Every sequence has one query
+        row - or, in a verify step of speculative decoding (``max_qlen`` > 1: the longest of
+        the batch), sequence s of ``md.num_decode`` has the rows ``md.seq_qstart[s]`` ..
+        ``md.seq_qstart[s + 1] - 1`` (its pending token and its drafts, at most 16 // G), the
+        attention is ``ops.attention_decode_mq`` (the multi-query kernel for the sequences with
+        drafts, the one-token kernel for those without; ``min_qlen``: the shortest qlen) and
+        ``temperature`` / ``seeds`` / ``steps`` are per row.
 
         Per layer: [RMSNorm+QKV+RoPE+KV-write] -> [paged attention, in-kernel split-K
         combine] -> [o_proj + residual add] -> [RMSNorm+gate_up+SiLU*up] ->
@@ -512,6 +519,10 @@ class LlamaModel:
         q = ws["q"][:B]
         attn = ws["attn"][:B]
         act = ws["act"][:B]
+        # verify step: which sequences the one-token and the multi-query kernel take (once
+        # per step, every layer's attention reuses it)
+        split = (ops.mq_split_kvlen(md.seq_kvlen, md.seq_qstart, md.num_decode)
+                 if max_qlen > 1 and min_qlen <= 1 and q.is_cuda else None)
         for li, L in enumerate(self.layers):
             ps = L.qkv_ps is not None
             if L.qkv_s is not None and not ps:
@@ -520,10 +531,17 @@ class LlamaModel:
             ops.decode_qkv_rope(residual, wq, eps, md.positions, md.slot_mapping, self.cos_sin,
                                 k_caches[li], v_caches[li], nq, nkv, q_out=q, preshuffled=ps,
                                 w_scale=L.qkv_s)
-            ops.attention_decode_v2(q, k_caches[li], v_caches[li], md.block_tables,
-                                    md.seq_kvlen, md.seq_qstart, self.scale, ws["part_out"],
-                                    ws["part_lse"], ws["counters"], ws["max_parts"],
-                                    ws["part_tokens"], out=attn, num_seqs=B)
+            if max_qlen > 1:
+                ops.attention_decode_mq(q, k_caches[li], v_caches[li], md.block_tables,
+                                        md.seq_kvlen, md.seq_qstart, self.scale, ws["part_out"],
+                                        ws["part_lse"], ws["counters"], ws["max_parts"],
+                                        ws["part_tokens"], out=attn, num_seqs=md.num_decode,
+                                        max_qlen=max_qlen, min_qlen=min_qlen, split=split)
+            else:
+                ops.attention_decode_v2(q, k_caches[li], v_caches[li], md.block_tables,
+                                        md.seq_kvlen, md.seq_qstart, self.scale, ws["part_out"],
+                                        ws["part_lse"], ws["counters"], ws["max_parts"],
+                                        ws["part_tokens"], out=attn, num_seqs=B)
             self._row_parallel(attn.view(B, nq * self.head_dim), L, "o", residual)
             ops.decode_gate_up_silu(residual, L.gate_up_ps if ps else L.gate_up, eps, out=act,
                                     preshuffled=ps, w_scale=L.gate_up_s)

@@ -999,3 +999,99 @@ def attention_decode_v2(q, k_cache, v_cache, block_tables, seq_kvlen, seq_qstart
                                   block_tables, seq_kvlen, seq_qstart, num_seqs, max_parts,
                                   part_tokens, q.shape[1], k_cache.shape[1], scale)
     return out
+
+
+# partition sizes of the multi-query decode kernel (attention_decode_mq.hip): the 16-wave
+# 512-token shape of the one-token kernel has no multi-query twin
+MQ_PART_TOKENS = (64, 128, 256)
+MQ_GROUPS = (1, 2, 3, 4, 8)
+
+
+def mq_max_qlen(g: int) -> int:
+    """Query tokens per sequence one multi-query decode launch takes: the GQA group's G heads
+    of each token share the kernel's 16 MFMA columns."""
+    return 16 // g
+
+
+def mq_split_kvlen(seq_kvlen, seq_qstart, num_seqs: int = -1):
+    """(kvlen of the one-token sequences, kvlen of the others), 0 elsewhere: the two kernels
+    of ``attention_decode_mq`` each skip the sequences whose kvlen is 0.  Device ops; a caller
+    that launches the op once per layer computes this once per step."""
+    n = seq_kvlen.shape[0] if num_seqs < 0 else num_seqs
+    one = (seq_qstart[1:n + 1] - seq_qstart[:n]) == 1
+    kv = seq_kvlen[:n]
+    zero = torch.zeros_like(kv)
+    return torch.where(one, kv, zero), torch.where(one, zero, kv)
+
+
+def attention_decode_mq(q, k_cache, v_cache, block_tables, seq_kvlen, seq_qstart, scale,
+                        part_out, part_lse, counters, max_parts, part_tokens, out=None,
+                        num_seqs: int = -1, max_qlen: int | None = None,
+                        min_qlen: int | None = None, split=None):
+    """Decode attention over 1 .. 16 // G query tokens per sequence (the verify step of
+    speculative decoding): sequence s owns rows seq_qstart[s] .. seq_qstart[s + 1] - 1, row j
+    of its qlen sits at position kvlen - qlen + j (``seq_kvlen`` counts this step's rows).
+    Same arguments as ``attention_decode_v2``.
+
+    Two launches over disjoint sequences: the one-token sequences run the one-token kernel
+    (``attention_decode_v2``'s) - a sequence without drafts gets what a plain decode step
+    computes, bit for bit - and the others the multi-query kernel; each kernel sees kvlen 0 for
+    the other's sequences and leaves their rows alone.  ``split`` = ``mq_split_kvlen(...)`` of
+    this step (computed here when None).  ``max_qlen`` / ``min_qlen``: the longest / shortest
+    qlen as the host built the launch - a kernel with no sequence is not launched; without
+    ``max_qlen`` it is read back from ``seq_qstart`` (a device synchronisation).  Out-of-range
+    shapes raise here: nothing is launched."""
+    g = q.shape[1] // k_cache.shape[1]
+    n = seq_kvlen.shape[0] if num_seqs < 0 else num_seqs
+    if q.shape[1] % k_cache.shape[1] or g not in MQ_GROUPS:
+        raise ValueError(f"attention_decode_mq: GQA group {q.shape[1]} / {k_cache.shape[1]} "
+                         f"not in {MQ_GROUPS}")
+    if part_tokens not in MQ_PART_TOKENS:
+        raise ValueError(f"attention_decode_mq: partitions of {MQ_PART_TOKENS} tokens "
+                         f"(got {part_tokens})")
+    if not 1 <= max_parts <= 64:
+        raise ValueError(f"attention_decode_mq: 1 .. 64 partitions (got {max_parts})")
+    if seq_qstart.shape[0] < n + 1:
+        raise ValueError("attention_decode_mq: seq_qstart needs num_seqs + 1 entries")
+    read_back = max_qlen is None or (DEBUG_CHECKS and not _capturing(seq_qstart))
+    if read_back and n:
+        qs = seq_qstart[:n + 1].long()
+        ql = qs[1:] - qs[:-1]
+        lo, hi, first, last = int(ql.min()), int(ql.max()), int(qs[0]), int(qs[-1])
+        if lo < 0 or first < 0 or last > q.shape[0]:
+            raise PagedArgsError(f"attention_decode_mq: query rows {first} .. {last} of "
+                                 f"{q.shape[0]}, shortest qlen {lo}")
+        if max_qlen is not None and hi > max_qlen:
+            raise PagedArgsError(f"attention_decode_mq: qlen {hi} in seq_qstart, caller said "
+                                 f"{max_qlen}")
+        if min_qlen is not None and lo < min_qlen:
+            raise PagedArgsError(f"attention_decode_mq: qlen {lo} in seq_qstart, caller said "
+                                 f">= {min_qlen}")
+        max_qlen = hi
+    if n and g * max_qlen > 16:
+        raise ValueError(f"attention_decode_mq: G * qlen = {g} * {max_qlen} > 16 MFMA columns")
+    check_paged_args(k_cache, block_tables, seq_kvlen, num_seqs, "attention_decode_mq")
+    if not q.is_cuda:
+        return ref.paged_attention(q, k_cache, v_cache, block_tables[:n], seq_kvlen[:n],
+                                   seq_qstart[:n + 1], scale, out=out)
+    out = torch.empty_like(q) if out is None else out
+    if n == 0:
+        return out
+    args = (q.shape[1], k_cache.shape[1], scale)
+    if max_qlen == 1:  # nothing but one-token sequences: a plain decode launch
+        _native().attention_decode_v2(out, part_out, part_lse, counters, q, k_cache, v_cache,
+                                      block_tables, seq_kvlen, seq_qstart, n, max_parts,
+                                      part_tokens, *args)
+        return out
+    if min_qlen is not None and min_qlen > 1:
+        kv_one, kv_multi = None, seq_kvlen
+    else:
+        kv_one, kv_multi = mq_split_kvlen(seq_kvlen, seq_qstart, n) if split is None else split
+    if kv_one is not None:
+        _native().attention_decode_v2(out, part_out, part_lse, counters, q, k_cache, v_cache,
+                                      block_tables, kv_one, seq_qstart, n, max_parts,
+                                      part_tokens, *args)
+    _native().attention_decode_mq(out, part_out, part_lse, counters, q, k_cache, v_cache,
+                                  block_tables, kv_multi, seq_qstart, n, max_parts,
+                                  part_tokens, *args)
+    return out

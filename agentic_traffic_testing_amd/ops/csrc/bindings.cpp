@@ -582,6 +582,36 @@ void attention_decode_v2(at::Tensor out, at::Tensor part_out, at::Tensor part_ls
            "attention_decode_v2");
 }
 
+void attention_decode_mq(at::Tensor out, at::Tensor part_out, at::Tensor part_lse,
+                         at::Tensor counters, const at::Tensor& q, const at::Tensor& k_cache,
+                         const at::Tensor& v_cache, const at::Tensor& block_tables,
+                         const at::Tensor& seq_kvlen, const at::Tensor& seq_qstart,
+                         int64_t num_seqs, int64_t max_parts, int64_t part_tokens,
+                         int64_t n_q_heads, int64_t n_kv_heads, double scale) {
+  check_dev(q, "q");
+  TORCH_CHECK(block_tables.scalar_type() == at::kInt && seq_kvlen.scalar_type() == at::kInt &&
+                  seq_qstart.scalar_type() == at::kInt && counters.scalar_type() == at::kInt,
+              "attention_decode_mq: int32 metadata");
+  if (num_seqs < 0) num_seqs = seq_kvlen.size(0);
+  TORCH_CHECK(num_seqs <= seq_kvlen.size(0) && num_seqs < seq_qstart.size(0),
+              "attention_decode_mq: num_seqs");
+  TORCH_CHECK(part_tokens == 64 || part_tokens == 128 || part_tokens == 256,
+              "attention_decode_mq: partitions of 64, 128 or 256 tokens");
+  TORCH_CHECK(part_out.numel() >= num_seqs * n_kv_heads * max_parts * 16 * 128 &&
+                  part_lse.numel() >= num_seqs * n_kv_heads * max_parts * 16 &&
+                  counters.numel() >= num_seqs * n_kv_heads,
+              "attention_decode_mq: workspace too small");
+  const at::DeviceGuard g(q.device());
+  check_rc(atta_attention_decode_mq(
+               out.data_ptr(), part_out.data_ptr<float>(), part_lse.data_ptr<float>(),
+               counters.data_ptr<int>(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+               block_tables.data_ptr<int>(), seq_kvlen.data_ptr<int>(), seq_qstart.data_ptr<int>(),
+               num_seqs, max_parts, part_tokens, n_q_heads, n_kv_heads, k_cache.size(3),
+               k_cache.size(2), block_tables.stride(0), q.stride(0), out.stride(0),
+               static_cast<float>(scale), dtype_code(q), cur_stream()),
+           "attention_decode_mq");
+}
+
 void set_gemv_trace(const c10::optional<at::Tensor>& trace) {
   if (trace.has_value() && trace->defined()) {
     TORCH_CHECK(trace->is_cuda() && trace->scalar_type() == at::kLong,
@@ -837,6 +867,11 @@ TORCH_LIBRARY(atta, m) {
       "Tensor seq_kvlen, Tensor seq_qstart, int num_seqs, int max_parts, int part_tokens, "
       "int n_q_heads, int n_kv_heads, float scale) -> ()");
   m.def(
+      "attention_decode_mq(Tensor(a!) out, Tensor(b!) part_out, Tensor(c!) part_lse, "
+      "Tensor(d!) counters, Tensor q, Tensor k_cache, Tensor v_cache, Tensor block_tables, "
+      "Tensor seq_kvlen, Tensor seq_qstart, int num_seqs, int max_parts, int part_tokens, "
+      "int n_q_heads, int n_kv_heads, float scale) -> ()");
+  m.def(
       "fused_qkv_rope(Tensor(a!) q_out, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor x, "
       "Tensor w, Tensor positions, Tensor slots, Tensor cos_sin, int n_q_heads, int n_kv_heads, "
       "float eps, int waves, bool preshuffled=False, Tensor? w_scale=None, int ksplit=1) -> ()");
@@ -920,5 +955,6 @@ TORCH_LIBRARY_IMPL(atta, CUDA, m) {
   m.impl("set_splitk_workspace", &set_splitk_workspace);
   m.impl("quant_rows_fp8", &quant_rows_fp8);
   m.impl("attention_decode_v2", &attention_decode_v2);
+  m.impl("attention_decode_mq", &attention_decode_mq);
   m.impl("skinny_variant", &skinny_variant);
 }

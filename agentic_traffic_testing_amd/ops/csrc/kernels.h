@@ -104,6 +104,17 @@ int atta_attention_decode_v2(void* out, float* part_out, float* part_lse, int* c
                              int64_t q_stride, int64_t out_stride, float scale, int dtype,
                              hipStream_t stream);
 
+// multi-query twin of atta_attention_decode_v2 (attention_decode_mq.hip): sequence s owns the
+// query rows seq_qstart[s] .. seq_qstart[s + 1] - 1, at most 16 / G of them; part_tokens 64,
+// 128 or 256
+int atta_attention_decode_mq(void* out, float* part_out, float* part_lse, int* counters,
+                             const void* q, const void* k_cache, const void* v_cache,
+                             const int* block_tables, const int* seq_kvlen, const int* seq_qstart,
+                             int num_seqs, int max_parts, int part_tokens, int n_q_heads,
+                             int n_kv_heads, int head_dim, int block_size, int bt_stride,
+                             int64_t q_stride, int64_t out_stride, float scale, int dtype,
+                             hipStream_t stream);
+
 int atta_skinny_variant(void* y, const void* x, const void* w, int M, int N, int K,
                         int variant, hipStream_t stream);
 

@@ -9,7 +9,9 @@ SURVEY §5.5.1).  Additions (new names only, nothing renamed):
 * ``llm_batch_size`` is actually observed (one sample per engine step; declared but never
   observed in the reference, serve_llm.py:121-125);
 * ``llm_engine_*`` gauges/counters: steps, running/waiting sequences, free KV blocks,
-  prefix-cache hits, step latency, engine heartbeat age.
+  prefix-cache hits, step latency, engine heartbeat age;
+* ``llm_spec_*`` counters (speculative decoding): verify steps, draft tokens verified,
+  draft tokens accepted - the engine's ``spec_stats``.
 """
 from __future__ import annotations
 
@@ -104,6 +106,25 @@ class LLMMetrics:
         self.heartbeat_age = Gauge(f"{p}_engine_heartbeat_age_seconds",
                                    "Seconds since the engine loop last made progress",
                                    registry=r)
+        self.spec_verify_steps = Counter(f"{p}_spec_verify_steps_total",
+                                         "Speculative decoding: verify steps run", registry=r)
+        self.spec_draft_tokens = Counter(f"{p}_spec_draft_tokens_total",
+                                         "Speculative decoding: draft tokens verified",
+                                         registry=r)
+        self.spec_accepted_tokens = Counter(f"{p}_spec_accepted_tokens_total",
+                                            "Speculative decoding: draft tokens accepted",
+                                            registry=r)
+        self._spec_seen = {"verify_steps": 0, "draft_tokens": 0, "accepted_tokens": 0}
+
+    def sync_spec(self, stats: dict):
+        """Advance the llm_spec_* counters to the engine's ``spec_stats`` totals."""
+        for key, ctr in (("verify_steps", self.spec_verify_steps),
+                         ("draft_tokens", self.spec_draft_tokens),
+                         ("accepted_tokens", self.spec_accepted_tokens)):
+            now = int(stats.get(key, 0))
+            if now > self._spec_seen[key]:
+                ctr.inc(now - self._spec_seen[key])
+            self._spec_seen[key] = now  # (a drop: the engine's statistics were reset)
 
     def record(self, status: str, latency_s: float, queue_wait_s: float, prompt_tokens,
                completion_tokens):

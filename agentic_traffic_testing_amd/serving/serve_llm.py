@@ -127,6 +127,7 @@ class ServerState:
         m.kv_free_blocks.set(info["free_blocks"])
         m.prefix_hits.set(info["prefix_hits"])
         m.prefix_queries.set(info["prefix_queries"])
+        m.sync_spec(getattr(self.engine, "spec_stats", None) or {})
         if self.aengine is not None:
             m.heartbeat_age.set(max(0.0, time.monotonic() - self.aengine.heartbeat))
 
@@ -418,6 +419,10 @@ def build_config(args):
         kw["burst_window_ms"] = args.burst_window_ms
     if getattr(args, "burst_gap_ms", None) is not None:
         kw["burst_gap_ms"] = args.burst_gap_ms
+    if getattr(args, "speculative", None) is not None:
+        kw["speculative"] = "" if args.speculative in ("off", "none") else args.speculative
+    if getattr(args, "num_speculative_tokens", None):
+        kw["spec_tokens"] = args.num_speculative_tokens
     return EngineConfig.from_env(**kw)
 
 
@@ -461,6 +466,9 @@ async def run_server(args) -> None:
     print(f"    max_num_seqs: {cfg.max_num_seqs}")
     print(f"    max_model_len: {cfg.max_model_len}")
     print(f"    tensor_parallel_size: {cfg.tensor_parallel_size}")
+    if cfg.speculative:
+        print(f"    speculative: {cfg.speculative}, {eng.runner.spec_tokens} drafts per step "
+              f"(<= {eng.runner.verify_rows()} rows)")
     print(f"    KV blocks: {eng.kv_cache_info()['num_gpu_blocks']} x {cfg.block_size} tokens")
     print(f"    init: {time.time() - t0:.1f}s")
     print("    Batching: ENABLED (continuous batching, chunked prefill, prefix caching)")
@@ -503,6 +511,12 @@ def make_parser() -> argparse.ArgumentParser:
                         "long for its siblings (0 = FIFO admission, like vLLM)")
     p.add_argument("--burst-gap-ms", type=float, default=None,
                    help="... closing early once no sibling arrived for this long")
+    p.add_argument("--speculative", choices=["ngram", "off"], default=None,
+                   help="speculative decoding: n-gram (prompt lookup) drafts verified in one "
+                        "decode step; outputs are those of plain decode (env LLM_SPECULATIVE)")
+    p.add_argument("--num-speculative-tokens", type=int, default=None,
+                   help="drafts per sequence and step, at most 16 // GQA group - 1 "
+                        "(default 3; env LLM_NUM_SPECULATIVE_TOKENS)")
     p.add_argument("--config", default=None,
                    help="YAML file of EngineConfig keys (e.g. llm/config/llama-3.1-8b.yaml); "
                         "explicit flags win")
