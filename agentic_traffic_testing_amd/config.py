@@ -259,7 +259,10 @@ class EngineConfig:
     # timed request (bench/coldstart.py: first 560-row prefill 1157 ms -> 11.5 ms without)
     startup_warmup: bool = True
     # "" = 16-bit weights; "fp8" = OCP e4m3fn weight-only quantisation with per-row scales
-    # (decode: fp8 GEMV kernels; prefill: hipBLASLt fp8 GEMM) - BASELINE config 5
+    # (decode: fp8 GEMV kernels; prefill: hipBLASLt fp8 GEMM) - BASELINE config 5; "mxfp4" =
+    # OCP Microscaling FP4 weight-only (e2m1 elements, e8m0 scale per 32): steps of at most 32
+    # rows stream 4.25 bits per weight, larger steps run 16-bit copies of the quantised values.
+    # Single GPU only
     quantization: str = ""
     num_kv_blocks: int = 0               # 0 = size from gpu_memory_utilization
     load_format: str = "auto"            # auto | dummy (random init) | safetensors
@@ -288,6 +291,11 @@ class EngineConfig:
     spec_ngram_min: int = 2
 
     def __post_init__(self):
+        if self.quantization not in ("", "fp8", "mxfp4"):
+            raise ValueError(f"quantization={self.quantization!r}: '', 'fp8' or 'mxfp4'")
+        if self.quantization == "mxfp4" and self.tensor_parallel_size > 1:
+            raise ValueError("quantization 'mxfp4' runs on one GPU: tensor_parallel_size "
+                             f"= {self.tensor_parallel_size} is not supported with it")
         if self.speculative not in ("", "ngram"):
             raise ValueError(f"speculative={self.speculative!r}: '' or 'ngram'")
         if self.speculative:

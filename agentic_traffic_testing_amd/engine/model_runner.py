@@ -136,6 +136,9 @@ class ModelRunner:
             self.model.load_safetensors(weights_dir)
         else:
             self.model.init_random(seed=cfg.seed)
+        if self.is_cuda and cfg.quantization == "mxfp4":
+            # the 4-bit copies first (always), so the room check below counts them
+            self.model.prepare_decode_weights(copies16=False)
         if self.is_cuda and ((cfg.fused_decode and cfg.preshuffle_decode_weights
                               and self._room_for_decode_copies())
                              or cfg.quantization == "fp8"):
@@ -530,7 +533,7 @@ class ModelRunner:
     def verify_rows(self) -> int:
         """Most rows (sequences + drafts) one verify step takes; 0: this runner cannot verify.
         On the GPU that is the largest row count the fused decode step runs (<= 128 rows on
-        pre-shuffled 16-bit weights, <= 32 on fp8) inside the workspace; the CPU backend runs
+        pre-shuffled 16-bit weights, <= 32 on fp8 and mxfp4) inside the workspace; the CPU backend runs
         verify steps through the reference ops."""
         if self._verify_rows is None:
             rows = 0
@@ -540,6 +543,8 @@ class ModelRunner:
                     ok = self.fused_decode and self.model.g in ops.MQ_GROUPS
                     while ok and rows > 1 and not self.model.decode_step_fusable(rows):
                         rows -= 1
+                    if self.model.quant == "mxfp4":  # verify steps stream the 4-bit copies
+                        rows = min(rows, ops.fused_max_rows(mxfp4=True))
                     rows = rows if ok and rows > 1 else 0
             self._verify_rows = rows
         return self._verify_rows

@@ -75,6 +75,17 @@ class LayerWeights:
     o_s: torch.Tensor | None = None
     gate_up_s: torch.Tensor | None = None
     down_s: torch.Tensor | None = None
+    # MXFP4 weight-only quantisation (GPU): the projections above hold the dequantised 16-bit
+    # values; these are the 4-bit decode copies (ops.preshuffle_mxfp4: packed e2m1 codes) and
+    # their e8m0 block scales, streamed by steps of at most 32 rows
+    qkv_w4: torch.Tensor | None = None
+    o_w4: torch.Tensor | None = None
+    gate_up_w4: torch.Tensor | None = None
+    down_w4: torch.Tensor | None = None
+    qkv_b4: torch.Tensor | None = None
+    o_b4: torch.Tensor | None = None
+    gate_up_b4: torch.Tensor | None = None
+    down_b4: torch.Tensor | None = None
 
 
 class LlamaModel:
@@ -82,9 +93,15 @@ class LlamaModel:
                  tp_size: int = 1, tp_group=None, quantization: str = ""):
         # tp_group: parallel.comm.TPComm (required when tp_size > 1)
         # quantization: "" (16-bit weights) | "fp8" (OCP e4m3fn weights, per-row scales; on the
-        # CPU reference path the dequantised values are stored instead)
-        if quantization not in ("", "fp8"):
+        # CPU reference path the dequantised values are stored instead) | "mxfp4" (OCP
+        # Microscaling FP4, weight-only: the projections are stored dequantised in 16 bits - every
+        # path computes with exactly the quantised values - and prepare_decode_weights() adds the
+        # 4-bit copies that steps of at most 32 rows stream; one GPU only)
+        if quantization not in ("", "fp8", "mxfp4"):
             raise ValueError(f"unsupported quantization {quantization!r}")
+        if quantization == "mxfp4" and tp_size > 1:
+            raise ValueError("quantization 'mxfp4' runs on one GPU: tensor parallelism is not "
+                             "supported with it")
         self.quant = quantization
         # prefill projections: "hipblaslt" (torch / hipBLASLt GEMMs) or "atta" (the
         # hand-written CDNA4 GEMM, ops/csrc/prefill_gemm.hip) for >= prefill_gemm_min_rows rows
@@ -204,6 +221,9 @@ class LlamaModel:
             amax = (wo.float().abs().amax(1) if full else None,
                     wd.float().abs().amax(1) if full else None)
             return self._quantize_layer(ones, qkv, o, gu, down, amax)
+        if self.quant == "mxfp4":  # the values MXFP4 can represent, in 16 bits
+            qkv, o, gu, down = (ops.dequantize_mxfp4(*ops.quantize_mxfp4(w), self.dtype)
+                                for w in (qkv, o, gu, down))
         return LayerWeights(ones, qkv, o, ones, gu, down)
 
     def _quantize_layer(self, ones, qkv, o, gu, down, amax=(None, None)) -> LayerWeights:
@@ -262,13 +282,30 @@ class LlamaModel:
         self._fold_final_norm()
         return self
 
-    def prepare_decode_weights(self):
+    def prepare_decode_weights(self, copies16: bool = True):
         """Build pre-shuffled copies of every decode-GEMV weight (row-major originals stay
         for the hipBLASLt prefill GEMMs): each wave load of the decode kernels then reads one
         contiguous 1 KiB instead of 16 rows x 64 B.  Costs one extra copy of the weights,
-        which 288 GB of HBM affords (16 GB for Llama-3-8B)."""
+        which 288 GB of HBM affords (16 GB for Llama-3-8B).
+
+        quantization="mxfp4" always builds the 4-bit copies as well (4.25 bits per weight on
+        top: re-quantising the stored values returns the codes they came from);
+        ``copies16=False`` then leaves the 16-bit pre-shuffled copies out (no room: steps
+        past 32 rows run from the row-major weights)."""
         if self.device.type != "cuda":
             return self
+        if self.quant == "mxfp4":
+            for L in self.layers:
+                if L.qkv_w4 is not None:
+                    continue
+                for proj, rowmap in (("qkv", "qkv"), ("o", "plain"), ("gate_up", "silu"),
+                                     ("down", "plain")):
+                    wq, sq = ops.preshuffle_mxfp4(*ops.quantize_mxfp4(getattr(L, proj)), rowmap)
+                    setattr(L, proj + "_w4", wq)
+                    setattr(L, proj + "_b4", sq)
+            if not copies16:
+                torch.cuda.synchronize(self.device)
+                return self
         for L in self.layers:
             if L.qkv_s is not None:  # fp8: 16-row x 64-col blocks of bytes
                 L.qkv_ps = ops.preshuffle_fp8(L.qkv, "qkv")
@@ -330,11 +367,11 @@ class LlamaModel:
         # SiLU-mul kernel that produced it
         plan = self.step_plan(T)
         for li, L in enumerate(self.layers):
-            ps = L.qkv_ps is not None
             if plan.qkv == FUSED:
-                q = ops.decode_qkv_rope(residual, L.qkv_ps if ps else L.qkv, eps, md.positions,
-                                        md.slot_mapping, self.cos_sin, k_caches[li],
-                                        v_caches[li], nq, nkv, preshuffled=ps, w_scale=L.qkv_s)
+                q = ops.decode_qkv_rope(residual, eps=eps, positions=md.positions,
+                                        slots=md.slot_mapping, cos_sin=self.cos_sin,
+                                        k_cache=k_caches[li], v_cache=v_caches[li], n_q_heads=nq,
+                                        n_kv_heads=nkv, **self._decode_w(L, "qkv", T))
             else:
                 if plan.fp8_chain:
                     if pending is None:
@@ -372,8 +409,7 @@ class LlamaModel:
                 continue
             self._proj_residual(plan.o, attn.view(T, nq * D), L, "o", residual)
             if plan.gate_up == FUSED:
-                a = ops.decode_gate_up_silu(residual, L.gate_up_ps if ps else L.gate_up, eps,
-                                            preshuffled=ps, w_scale=L.gate_up_s)
+                a = ops.decode_gate_up_silu(residual, eps=eps, **self._decode_w(L, "gate_up", T))
             elif L.gate_up_s is not None:
                 # fp8 gate_up of a fused step past its crossover: an fp8 GEMM on row-quantised
                 # activations (norm fused into the quantiser), bf16 SiLU-mul for the fused down
@@ -403,6 +439,21 @@ class LlamaModel:
     _PG_AUTO_UNTUNED = sp.PG_AUTO_UNTUNED
     _PG_SPLITK = sp.PG_SPLITK
     gemm_tuned = False  # set by the model runner when a tuned library table is loaded
+
+    def _w4_rows(self, T: int) -> bool:
+        """Does a T-row step stream the MXFP4 copies (the 4-bit build of the 16-row-tile GEMV)?"""
+        return (self.quant == "mxfp4" and bool(self.layers) and self.layers[0].qkv_w4 is not None
+                and ops.fused_kernel(T, True, mxfp4=True) is not None)
+
+    def _decode_w(self, L: LayerWeights, proj: str, T: int) -> dict:
+        """The weight arguments of a fused op for a T-row step: the 4-bit copy with its block
+        scales, else the pre-shuffled copy (fp8: with its row scales), else the row-major
+        weight."""
+        if self._w4_rows(T):
+            return {"w": getattr(L, proj + "_w4"), "w_block_scale": getattr(L, proj + "_b4")}
+        ps = L.qkv_ps is not None
+        return {"w": getattr(L, proj + "_ps") if ps else getattr(L, proj), "preshuffled": ps,
+                "w_scale": getattr(L, proj + "_s")}
 
     def step_plan(self, T: int) -> sp.StepPlan:
         """The backend of each projection of a T-row prefill / mixed step, whether it runs the
@@ -524,13 +575,12 @@ class LlamaModel:
         split = (ops.mq_split_kvlen(md.seq_kvlen, md.seq_qstart, md.num_decode)
                  if max_qlen > 1 and min_qlen <= 1 and q.is_cuda else None)
         for li, L in enumerate(self.layers):
-            ps = L.qkv_ps is not None
-            if L.qkv_s is not None and not ps:
+            if L.qkv_s is not None and L.qkv_ps is None:
                 raise RuntimeError("fp8 decode needs prepare_decode_weights()")
-            wq = L.qkv_ps if ps else L.qkv
-            ops.decode_qkv_rope(residual, wq, eps, md.positions, md.slot_mapping, self.cos_sin,
-                                k_caches[li], v_caches[li], nq, nkv, q_out=q, preshuffled=ps,
-                                w_scale=L.qkv_s)
+            ops.decode_qkv_rope(residual, eps=eps, positions=md.positions,
+                                slots=md.slot_mapping, cos_sin=self.cos_sin,
+                                k_cache=k_caches[li], v_cache=v_caches[li], n_q_heads=nq,
+                                n_kv_heads=nkv, q_out=q, **self._decode_w(L, "qkv", B))
             if max_qlen > 1:
                 ops.attention_decode_mq(q, k_caches[li], v_caches[li], md.block_tables,
                                         md.seq_kvlen, md.seq_qstart, self.scale, ws["part_out"],
@@ -543,8 +593,8 @@ class LlamaModel:
                                         ws["part_lse"], ws["counters"], ws["max_parts"],
                                         ws["part_tokens"], out=attn, num_seqs=B)
             self._row_parallel(attn.view(B, nq * self.head_dim), L, "o", residual)
-            ops.decode_gate_up_silu(residual, L.gate_up_ps if ps else L.gate_up, eps, out=act,
-                                    preshuffled=ps, w_scale=L.gate_up_s)
+            ops.decode_gate_up_silu(residual, eps=eps, out=act,
+                                    **self._decode_w(L, "gate_up", B))
             self._row_parallel(act, L, "down", residual)
         if top_p is not None:
             logits = self.compute_logits(ops.rms_norm(residual, self.norm, eps))
@@ -559,6 +609,11 @@ class LlamaModel:
         kernel adds the rank-order sum into the residual (X1 / X2, <= 32 rows), else the
         product goes through the all-reduce whose epilogue adds it (IPC one- / two-shot, or
         RCCL)."""
+        if self._w4_rows(x.shape[0]):  # MXFP4: one GPU only
+            ops.linear(x, getattr(L, proj + "_w4"), residual=residual,
+                       waves=ops.decode_waves(proj, mxfp4=True), ksplit=None, proj=proj,
+                       w_block_scale=getattr(L, proj + "_b4"))
+            return
         ps = L.qkv_ps is not None
         w = getattr(L, proj + "_ps") if ps else getattr(L, proj)
         scale = getattr(L, proj + "_s")

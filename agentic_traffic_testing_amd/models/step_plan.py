@@ -33,6 +33,8 @@ and ``fused_decode`` on, every projection's K in whole wave steps, ``ATTA_WIDE_M
 | fp8, other widths    | 1   | 1-128              | fused | fused       | fused       | fused    |
 | fp8                  | 1   | MIDM_FP8_ROWS (off)| fused | fused       | lib [3]     | fused    |
 | fp8                  | any | the rest [4]       | lib   | lib         | lib [1]     | lib      |
+| mxfp4                | 1   | 1-32               | fused | fused       | fused       | fused    |
+| mxfp4                | 1   | the rest [5]       | as the 16-bit rows above                      |
 
 [1] no tuned library table loaded: ``gemm`` from 2048 rows (bf16) / 2560 rows (fp8).
 [2] no tuned library table loaded, TP = 1, bf16: ``gemm_splitk`` at 448-1152 rows.
@@ -41,6 +43,10 @@ and ``fused_decode`` on, every projection's K in whole wave steps, ``ATTA_WIDE_M
 [4] the activation-quantised fp8 chain (``fp8_chain``): every GEMM's activation operand comes
     quantised out of the norm / SiLU-mul kernel before it, and each down product is deferred
     into the next norm + quant kernel.
+
+[5] ``quantization="mxfp4"`` keeps the projections dequantised in 16 bits, so a step past the
+    4-bit GEMV's 32 rows is planned exactly as the same model without quantisation (pre-shuffled
+    or row-major, whichever 16-bit copies exist); at most 32 rows stream the 4-bit copies.
 
 fp8 weights are always pre-shuffled on a GPU (without the copies no fp8 step runs fused).  With
 the fused path off (either switch, a K that is not whole wave steps, the kernel limits) a step
@@ -53,7 +59,7 @@ takes "the rest" rows; 16-bit weights other than bf16 never take ``gemm``.
 from __future__ import annotations
 
 import os
-from dataclasses import dataclass, field
+from dataclasses import dataclass, field, replace
 
 import torch
 
@@ -122,7 +128,7 @@ class StepFacts:
     """What decides a step's plan besides its rows: fixed for a step, the same for every layer.
     Widths are this TP rank's."""
     gpu: bool                   # a GPU model (the CPU reference runs the library ops)
-    quant: str                  # "" | "fp8"
+    quant: str                  # "" | "fp8" | "mxfp4"
     wdtype: torch.dtype         # the projections' storage dtype (fp8 on a GPU: torch.uint8)
     tp_size: int
     preshuffled: bool           # prepare_decode_weights() built the pre-shuffled copies
@@ -167,15 +173,18 @@ class StepPlan:
 
 def proj_dims_ok(gpu: bool, quant: str, hidden: int, q_width: int, inter: int) -> bool:
     """Every projection's K in whole wave steps of the weight-streaming kernels (16-bit GEMVs:
-    K % 128 = 4 waves x 32; fp8: K % 256 = 4 waves x 64)."""
+    K % 128 = 4 waves x 32; fp8: K % 256 = 4 waves x 64; mxfp4: K % 128 = one 128-wide lane
+    load - the loads need not divide evenly among the waves)."""
     step = 256 if quant == "fp8" else 128
     return gpu and hidden % step == 0 and inter % step == 0 and q_width % step == 0
 
 
 def proj_fusable(T: int, dims_ok: bool, tp_size: int, preshuffled: bool, quant: str) -> bool:
     """LlamaModel.proj_fusable."""
-    return (dims_ok and (tp_size == 1 or T <= ops.WIDE_ROWS)
-            and ops.fused_kernel(T, preshuffled, preshuffled and quant == "fp8") is not None)
+    kernel = ops.fused_kernel(T, preshuffled, preshuffled and quant == "fp8")
+    if kernel is None and quant == "mxfp4":
+        kernel = ops.fused_kernel(T, True, mxfp4=True)
+    return dims_ok and (tp_size == 1 or T <= ops.WIDE_ROWS) and kernel is not None
 
 
 def _lib_or_gemm(T: int, f: StepFacts, proj: str, mode: int) -> str:
@@ -200,6 +209,11 @@ def _lib_or_gemm(T: int, f: StepFacts, proj: str, mode: int) -> str:
 
 def step_plan(T: int, f: StepFacts) -> StepPlan:
     """The plan of a T-row prefill / mixed step (the table in the module comment)."""
+    if f.quant == "mxfp4":
+        if (f.gpu and f.tp_size == 1 and f.small_prefill_fused and f.fused_decode and f.dims_ok
+                and ops.fused_kernel(T, True, mxfp4=True) is not None):
+            return StepPlan(FUSED, FUSED, FUSED, FUSED, fp8_chain=False, pad_rows=False)
+        return step_plan(T, replace(f, quant=""))
     fp8 = f.quant == "fp8" and f.gpu
     tp1 = f.tp_size == 1
     wide = ops.WIDE_ROWS

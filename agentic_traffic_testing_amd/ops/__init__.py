@@ -410,15 +410,19 @@ def _policy_tops() -> tuple[int, int, int]:
     return min(SKINNY_MAX_M, SKINNY_ROWS), wide_top, (midm_top if midm_top > WIDE_ROWS else 0)
 
 
-def fused_kernel(m: int, preshuffled: bool, fp8: bool = False, epi: str = "plain") -> str | None:
+def fused_kernel(m: int, preshuffled: bool, fp8: bool = False, epi: str = "plain",
+                 mxfp4: bool = False) -> str | None:
     """Which hand-written weight-streaming kernel runs ``m`` rows over this weight layout with
     this epilogue ("plain" | "resadd" | "qkv" | "silu" | "sample" | "push"): "skinny" (the
     16-row-tile GEMV), "wide", "midm", or None (no kernel: the native call would fail).  The
     routing table of csrc/gemv.hip ``route()`` (written out there and in docs/kernels.md)
-    under the policy limits above.  Pure: no native call, usable without a GPU."""
+    under the policy limits above.  ``mxfp4``: the 4-bit copies (``preshuffle_mxfp4``), which
+    only the 16-row-tile GEMV streams.  Pure: no native call, usable without a GPU."""
     skinny_top, wide_top, midm_top = _policy_tops()
     if m < 1:
         return None
+    if mxfp4:
+        return "skinny" if m <= skinny_top and epi not in ("sample", "push") else None
     if not (preshuffled or fp8) or epi == "push" or not wide_top:
         return "skinny" if m <= skinny_top else None
     if m <= SKINNY_ROWS and (fp8 or m < _wide_min_rows[1 if epi == "silu" else 0]):
@@ -430,11 +434,12 @@ def fused_kernel(m: int, preshuffled: bool, fp8: bool = False, epi: str = "plain
     return "midm" if epi != "sample" and WIDE_ROWS < m <= midm_top else None
 
 
-def fused_max_rows(preshuffled: bool = True) -> int:
+def fused_max_rows(preshuffled: bool = True, mxfp4: bool = False) -> int:
     """Most rows a projection (any epilogue but the sampler's) may have to run on the
-    hand-written weight-streaming kernels: row-major weights, or pre-shuffled 16-bit / fp8."""
+    hand-written weight-streaming kernels: row-major weights or the MXFP4 copies (the
+    16-row-tile GEMV alone), or pre-shuffled 16-bit / fp8."""
     tops = _policy_tops()
-    return max(tops) if preshuffled else tops[0]
+    return max(tops) if preshuffled and not mxfp4 else tops[0]
 
 
 SKINNY_WAVES = int(os.environ.get("ATTA_SKINNY_WAVES", "8"))
@@ -446,11 +451,14 @@ WAVES_LARGE = int(os.environ.get("ATTA_WAVES_LARGE", "16"))
 # Workgroup waves per decode projection and weight format, from cold-cache sweeps on MI355X
 # (profiles/r1_microbench_v5_cold_preshuffle.txt, r1_microbench_v6_fp8.txt, and the
 # pre-shuffled unroll sweep): "rm" row-major 16-bit, "ps" pre-shuffled 16-bit, "fp8".
+# "mxfp4": not swept - a wave owns whole 128-wide loads, so K 4096 is 32 loads (4 per wave at
+# 8 waves) and the 8B down projection 112 (7 per wave at 16); the library halves the count
+# when a slice has fewer loads than waves.
 DECODE_WAVES = {
-    "qkv": {"rm": 8, "ps": 4, "fp8": 8},
-    "o": {"rm": 8, "ps": 8, "fp8": 8},
-    "gate_up": {"rm": 16, "ps": 16, "fp8": 8},
-    "down": {"rm": 16, "ps": 8, "fp8": 16},
+    "qkv": {"rm": 8, "ps": 4, "fp8": 8, "mxfp4": 8},
+    "o": {"rm": 8, "ps": 8, "fp8": 8, "mxfp4": 8},
+    "gate_up": {"rm": 16, "ps": 16, "fp8": 8, "mxfp4": 8},
+    "down": {"rm": 16, "ps": 8, "fp8": 16, "mxfp4": 16},
     "lm_head": {"rm": 16, "ps": 16, "fp8": 16},
 }
 # tuning override: ATTA_DECODE_WAVES="qkv.ps=8,down.fp8=16"
@@ -466,7 +474,10 @@ for _item in filter(None, os.environ.get("ATTA_DECODE_WAVES", "").split(",")):
 DECODE_WAVES_MT2 = {"gate_up": 8}
 
 
-def decode_waves(proj: str, preshuffled: bool = False, fp8: bool = False, m: int = 0) -> int:
+def decode_waves(proj: str, preshuffled: bool = False, fp8: bool = False, m: int = 0,
+                 mxfp4: bool = False) -> int:
+    if mxfp4:
+        return DECODE_WAVES[proj]["mxfp4"]
     if m > 16 and preshuffled and not fp8 and proj in DECODE_WAVES_MT2:
         return DECODE_WAVES_MT2[proj]
     return DECODE_WAVES[proj]["fp8" if fp8 else ("ps" if preshuffled else "rm")]
@@ -535,11 +546,14 @@ def _ksplit(proj: str, x: torch.Tensor, ksplit: int | None, tiles: int) -> int:
 
 
 def skinny_ok(x: torch.Tensor, w: torch.Tensor, preshuffled: bool = False,
-              fp8: bool = False) -> bool:
+              fp8: bool = False, mxfp4: bool = False) -> bool:
     """Does ``x @ w.T`` run on the hand-written MFMA kernels?  Shapes they take, and a row
-    count ``fused_kernel`` names a kernel for."""
+    count ``fused_kernel`` names a kernel for.  ``mxfp4``: ``w`` holds the packed codes
+    [N, K / 2] of ``preshuffle_mxfp4``."""
     m, k = x.shape
-    return (x.is_cuda and fused_kernel(m, preshuffled, fp8) is not None
+    if mxfp4 and (w.dtype != torch.uint8 or w.shape[1] * 2 != k):
+        return False
+    return (x.is_cuda and fused_kernel(m, preshuffled, fp8, mxfp4=mxfp4) is not None
             and w.shape[0] % 16 == 0 and k % 128 == 0 and x.stride(1) == 1
             and w.is_contiguous())
 
@@ -656,6 +670,51 @@ def preshuffle_fp8(q: torch.Tensor, rowmap: str = "plain") -> torch.Tensor:
         q = q.index_select(0, rows)
     return (q.reshape(N // 16, 16, K // 64, 2, 4, 8).permute(0, 2, 4, 1, 3, 5).contiguous()
             .reshape(N, K))
+
+
+# ---- MXFP4 weight-only quantisation (OCP Microscaling: e2m1 elements, e8m0 block scales) ----
+MXFP4_BLOCK = ref.MXFP4_BLOCK
+quantize_mxfp4 = ref.quantize_mxfp4
+dequantize_mxfp4 = ref.dequantize_mxfp4
+
+
+def preshuffle_mxfp4(codes: torch.Tensor, scales: torch.Tensor, rowmap: str = "plain"
+                     ) -> tuple[torch.Tensor, torch.Tensor]:
+    """MXFP4 analogue of ``preshuffle``: (codes uint8 [N, K], scales uint8 [N, K / 32]) ->
+    (wq uint8 [N, K / 2], sq uint8 [N, K / 32]) as the 4-bit decode GEMV streams them.  Rows
+    permuted by ``rowmap``; per 16-row tile and 128-wide K chunk c, lane l's 16 bytes are row
+    l & 15 of the chunk's four 32-wide K steps: dword j holds k = 128 c + 32 j + 8 (l >> 4) + i,
+    code i in bits 4i .. 4i + 3.  ``sq``: 64 B per tile and chunk, one dword per row, byte j =
+    the scale of K step j.  ``unshuffle_mxfp4`` inverts it."""
+    N, K = codes.shape
+    if N % 16 or K % 128 or scales.shape != (N, K // MXFP4_BLOCK):
+        raise ValueError(f"mxfp4 preshuffle needs N % 16 == 0, K % 128 == 0 and scales "
+                         f"[N, K / 32], got {tuple(codes.shape)} / {tuple(scales.shape)}")
+    rows = _rowmap_index(N, rowmap, codes.device)
+    if rows is not None:
+        codes, scales = codes.index_select(0, rows), scales.index_select(0, rows)
+    # (tile, row, chunk, step j, lane group g, element i) -> (tile, chunk, g, row, j, i)
+    c = codes.reshape(N // 16, 16, K // 128, 4, 4, 8).permute(0, 2, 4, 1, 3, 5)
+    wq = (c[..., 0::2] | (c[..., 1::2] << 4)).contiguous().reshape(N, K // 2)
+    sq = scales.reshape(N // 16, 16, K // 128, 4).permute(0, 2, 1, 3).contiguous()
+    return wq, sq.reshape(N, K // MXFP4_BLOCK)
+
+
+def unshuffle_mxfp4(wq: torch.Tensor, sq: torch.Tensor, rowmap: str = "plain"
+                    ) -> tuple[torch.Tensor, torch.Tensor]:
+    """Inverse of ``preshuffle_mxfp4``: (codes uint8 [N, K], scales uint8 [N, K / 32])."""
+    N, K = wq.shape[0], wq.shape[1] * 2
+    p = wq.reshape(N // 16, K // 128, 4, 16, 4, 4)
+    c = torch.stack([p & 15, p >> 4], -1).reshape(N // 16, K // 128, 4, 16, 4, 8)
+    codes = c.permute(0, 3, 1, 4, 2, 5).contiguous().reshape(N, K)
+    scales = (sq.reshape(N // 16, K // 128, 16, 4).permute(0, 2, 1, 3).contiguous()
+              .reshape(N, K // MXFP4_BLOCK))
+    rows = _rowmap_index(N, rowmap, wq.device)
+    if rows is not None:
+        inv = torch.empty_like(rows)
+        inv[rows] = torch.arange(N, device=rows.device)
+        codes, scales = codes.index_select(0, inv), scales.index_select(0, inv)
+    return codes, scales
 
 
 def _rowmap_index(N: int, rowmap: str, dev):
@@ -846,29 +905,33 @@ def _need_cuda(x, preshuffled):
 def linear(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor | None = None,
            out: torch.Tensor | None = None, waves: int | None = None,
            preshuffled: bool = False, w_scale: torch.Tensor | None = None,
-           ksplit: int | None = 1, proj: str = "") -> torch.Tensor:
+           ksplit: int | None = 1, proj: str = "",
+           w_block_scale: torch.Tensor | None = None) -> torch.Tensor:
     """y = x @ w.T.  With ``residual`` the product is added to ``residual`` IN PLACE and
     ``residual`` is returned (residual-stream update).  Decode-sized M runs the MFMA skinny
     GEMM; everything else (prefill, CPU) runs F.linear (hipBLASLt on the GPU).
     ``preshuffled``: ``w`` comes from ``preshuffle`` (skinny path only).
-    ``w_scale``: ``w`` is fp8 (uint8, ``preshuffle_fp8`` layout) with this per-row scale."""
-    _need_cuda(x, preshuffled or w_scale is not None)
+    ``w_scale``: ``w`` is fp8 (uint8, ``preshuffle_fp8`` layout) with this per-row scale.
+    ``w_block_scale``: ``w`` / this are the MXFP4 codes / block scales of
+    ``preshuffle_mxfp4`` (at most 32 rows: the 16-row-tile GEMV alone streams them)."""
+    mxfp4 = w_block_scale is not None
+    _need_cuda(x, preshuffled or w_scale is not None or mxfp4)
     fp8 = w_scale is not None
-    if fp8:
+    if fp8 or mxfp4:
         preshuffled = True
-    fused = skinny_ok(x, w, preshuffled, fp8)
+    fused = skinny_ok(x, w, preshuffled, fp8, mxfp4)
     if preshuffled and not fused:
         raise ValueError("pre-shuffled weights need the skinny (decode) path")
     if fused:
         ksplit = _ksplit(proj, x, ksplit, w.shape[0] // 16)
         if residual is not None:
             _native().skinny_gemm(residual, x, w, residual, waves or SKINNY_WAVES, preshuffled,
-                                  w_scale, ksplit)
+                                  w_scale, ksplit, w_block_scale)
             return residual
         if out is None:
             out = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)
         _native().skinny_gemm(out, x, w, None, waves or SKINNY_WAVES, preshuffled, w_scale,
-                              ksplit)
+                              ksplit, w_block_scale)
         return out
     if residual is not None:
         # hipBLASLt C-matrix epilogue: residual = residual + x @ w.T in one GEMM (fp32
@@ -904,9 +967,12 @@ def linear_push_reduce(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor,
 
 # ---- fused decode-step ops (norm weight folded into W on the host) -----------------------
 def decode_qkv_rope(x, w, eps, positions, slots, cos_sin, k_cache, v_cache, n_q_heads,
-                    n_kv_heads, q_out=None, preshuffled=False, w_scale=None, ksplit=None):
-    """RMSNorm(x) -> QKV GEMM -> RoPE -> q out + paged K/V write, one kernel on the GPU."""
-    _need_cuda(x, preshuffled or w_scale is not None)
+                    n_kv_heads, q_out=None, preshuffled=False, w_scale=None, ksplit=None,
+                    w_block_scale=None, waves=None):
+    """RMSNorm(x) -> QKV GEMM -> RoPE -> q out + paged K/V write, one kernel on the GPU.
+    ``w_block_scale``: MXFP4 weights (``preshuffle_mxfp4``, row map "qkv")."""
+    mxfp4 = w_block_scale is not None
+    _need_cuda(x, preshuffled or w_scale is not None or mxfp4)
     check_slots(k_cache, slots[:x.shape[0]], "decode_qkv_rope")
     if q_out is None:
         q_out = torch.empty(x.shape[0], n_q_heads, 128, dtype=x.dtype, device=x.device)
@@ -918,15 +984,19 @@ def decode_qkv_rope(x, w, eps, positions, slots, cos_sin, k_cache, v_cache, n_q_
         return q_out
     _native().fused_qkv_rope(q_out, k_cache, v_cache, x, w, positions, slots, cos_sin,
                              n_q_heads, n_kv_heads, eps,
-                             decode_waves("qkv", preshuffled, w_scale is not None),
-                             preshuffled or w_scale is not None, w_scale,
-                             _ksplit("qkv", x, ksplit, w.shape[0] // 16))
+                             waves or decode_waves("qkv", preshuffled, w_scale is not None,
+                                                   mxfp4=mxfp4),
+                             preshuffled or w_scale is not None or mxfp4, w_scale,
+                             _ksplit("qkv", x, ksplit, w.shape[0] // 16), w_block_scale)
     return q_out
 
 
-def decode_gate_up_silu(x, w, eps, out=None, preshuffled=False, w_scale=None, ksplit=None):
-    """RMSNorm(x) -> gate_up GEMM -> SiLU(gate) * up, one kernel on the GPU."""
-    _need_cuda(x, preshuffled or w_scale is not None)
+def decode_gate_up_silu(x, w, eps, out=None, preshuffled=False, w_scale=None, ksplit=None,
+                        w_block_scale=None, waves=None):
+    """RMSNorm(x) -> gate_up GEMM -> SiLU(gate) * up, one kernel on the GPU.
+    ``w_block_scale``: MXFP4 weights (``preshuffle_mxfp4``, row map "silu")."""
+    mxfp4 = w_block_scale is not None
+    _need_cuda(x, preshuffled or w_scale is not None or mxfp4)
     inter = w.shape[0] // 2
     if out is None:
         out = torch.empty(x.shape[0], inter, dtype=x.dtype, device=x.device)
@@ -934,9 +1004,11 @@ def decode_gate_up_silu(x, w, eps, out=None, preshuffled=False, w_scale=None, ks
         n = ref.rms_norm(x, torch.ones(x.shape[1], dtype=x.dtype), eps)
         out.copy_(ref.silu_and_mul(torch.nn.functional.linear(n, w)))
         return out
-    waves = decode_waves("gate_up", preshuffled, w_scale is not None, m=x.shape[0])
-    _native().fused_gate_up_silu(out, x, w, eps, waves, preshuffled or w_scale is not None,
-                                 w_scale, _ksplit("gate_up", x, ksplit, w.shape[0] // 16))
+    waves = waves or decode_waves("gate_up", preshuffled, w_scale is not None, m=x.shape[0],
+                                  mxfp4=mxfp4)
+    _native().fused_gate_up_silu(out, x, w, eps, waves,
+                                 preshuffled or w_scale is not None or mxfp4, w_scale,
+                                 _ksplit("gate_up", x, ksplit, w.shape[0] // 16), w_block_scale)
     return out
 
 

@@ -293,6 +293,29 @@ const float* fp8_scale(const at::Tensor& w, const c10::optional<at::Tensor>& w_s
   return w_scale->data_ptr<float>();
 }
 
+// MXFP4 weight-only quantisation: w is uint8 [N, K / 2] (two e2m1 codes per byte, in the
+// layout of ops.preshuffle_mxfp4) and w_block_scale uint8 [N, K / 32] (e8m0, same layout
+// family); returns the block-scale pointer (nullptr: not MXFP4 weights).
+const uint8_t* mxfp4_scale(const at::Tensor& x, const at::Tensor& w,
+                           const c10::optional<at::Tensor>& w_scale,
+                           const c10::optional<at::Tensor>& w_block_scale, const char* what) {
+  if (!w_block_scale.has_value() || !w_block_scale->defined()) return nullptr;
+  TORCH_CHECK(!w_scale.has_value() || !w_scale->defined(), what,
+              ": w_scale (fp8) and w_block_scale (mxfp4) exclude each other");
+  check_dev(x, "x");
+  const int64_t K = x.dim() == 2 ? x.size(1) : 0;
+  TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && K >= 128 && K % 128 == 0, what,
+              ": mxfp4 weights need 2-D x with K % 128 == 0");
+  TORCH_CHECK(w.scalar_type() == at::kByte && w.dim() == 2 && w.is_contiguous() && w.is_cuda() &&
+                  w.size(0) % 16 == 0 && w.size(1) * 2 == K,
+              what, ": mxfp4 codes must be uint8 [N, K / 2] on the GPU, N % 16 == 0");
+  TORCH_CHECK(w_block_scale->scalar_type() == at::kByte && w_block_scale->is_contiguous() &&
+                  w_block_scale->is_cuda() && w_block_scale->dim() == 2 &&
+                  w_block_scale->size(0) == w.size(0) && w_block_scale->size(1) * 32 == K,
+              what, ": mxfp4 block scales must be uint8 [N, K / 32] on the GPU");
+  return w_block_scale->data_ptr<uint8_t>();
+}
+
 // dtype code for the skinny GEMV entry points; bit 8 flags pre-shuffled weights (kPreshuffled)
 int skinny_dtype(const at::Tensor& x, bool preshuffled) {
   return dtype_code(x) | (preshuffled ? kPreshuffled : 0);
@@ -300,16 +323,19 @@ int skinny_dtype(const at::Tensor& x, bool preshuffled) {
 
 void skinny_gemm(at::Tensor y, const at::Tensor& x, const at::Tensor& w,
                  const c10::optional<at::Tensor>& residual, int64_t waves, bool preshuffled,
-                 const c10::optional<at::Tensor>& w_scale, int64_t ksplit) {
+                 const c10::optional<at::Tensor>& w_scale, int64_t ksplit,
+                 const c10::optional<at::Tensor>& w_block_scale) {
   check_dev(x, "x");
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && y.dim() == 2, "skinny_gemm: 2-D operands");
   TORCH_CHECK(x.stride(1) == 1 && y.stride(1) == 1 && w.is_contiguous(), "skinny_gemm: layout");
-  TORCH_CHECK(x.size(1) == w.size(1) && y.size(0) == x.size(0) && y.size(1) == w.size(0),
+  const uint8_t* bs = mxfp4_scale(x, w, w_scale, w_block_scale, "skinny_gemm");
+  TORCH_CHECK((bs != nullptr || x.size(1) == w.size(1)) && y.size(0) == x.size(0) &&
+                  y.size(1) == w.size(0),
               "skinny_gemm: shapes");
   TORCH_CHECK((x.scalar_type() == w.scalar_type() || w.scalar_type() == at::kByte) &&
                   y.scalar_type() == x.scalar_type(),
               "skinny_gemm: dtypes");
-  const float* ws = fp8_scale(w, w_scale, "skinny_gemm");
+  const float* ws = bs != nullptr ? nullptr : fp8_scale(w, w_scale, "skinny_gemm");
   const void* r = nullptr;
   int64_t rs = 0;
   if (residual.has_value() && residual->defined()) {
@@ -319,7 +345,7 @@ void skinny_gemm(at::Tensor y, const at::Tensor& x, const at::Tensor& w,
   }
   const at::DeviceGuard g(x.device());
   check_rc(atta_skinny_gemm(y.data_ptr(), x.data_ptr(), w.data_ptr(), r, x.size(0), w.size(0),
-                            w.size(1), x.stride(0), y.stride(0), rs, waves, ksplit, ws,
+                            x.size(1), x.stride(0), y.stride(0), rs, waves, ksplit, ws, bs,
                             skinny_dtype(x, preshuffled), cur_stream()),
            "skinny_gemm");
 }
@@ -412,12 +438,13 @@ void prefill_gemm_config(int64_t schedule, int64_t group_m, int64_t ablate) {
            "prefill_gemm_config");
 }
 
-void check_skinny(const at::Tensor& x, const at::Tensor& w, const char* what) {
+void check_skinny(const at::Tensor& x, const at::Tensor& w, const char* what,
+                  bool mxfp4 = false) {
   TORCH_CHECK(w.size(0) % 16 == 0 && w.size(1) % 32 == 0, what, ": weight tile shape");
   check_dev(x, "x");
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && x.stride(1) == 1 && w.is_contiguous(), what,
               ": layout");
-  TORCH_CHECK(x.size(1) == w.size(1) &&
+  TORCH_CHECK(x.size(1) == (mxfp4 ? 2 : 1) * w.size(1) &&
                   (x.scalar_type() == w.scalar_type() || w.scalar_type() == at::kByte),
               what, ": shapes / dtypes");
 }
@@ -426,9 +453,10 @@ void fused_qkv_rope(at::Tensor q_out, at::Tensor k_cache, at::Tensor v_cache, co
                     const at::Tensor& w, const at::Tensor& positions, const at::Tensor& slots,
                     const at::Tensor& cos_sin, int64_t n_q_heads, int64_t n_kv_heads, double eps,
                     int64_t waves, bool preshuffled, const c10::optional<at::Tensor>& w_scale,
-                    int64_t ksplit) {
-  check_skinny(x, w, "fused_qkv_rope");
-  const float* ws = fp8_scale(w, w_scale, "fused_qkv_rope");
+                    int64_t ksplit, const c10::optional<at::Tensor>& w_block_scale) {
+  const uint8_t* bs = mxfp4_scale(x, w, w_scale, w_block_scale, "fused_qkv_rope");
+  check_skinny(x, w, "fused_qkv_rope", bs != nullptr);
+  const float* ws = bs != nullptr ? nullptr : fp8_scale(w, w_scale, "fused_qkv_rope");
   TORCH_CHECK(w.size(0) == (n_q_heads + 2 * n_kv_heads) * 128, "fused_qkv_rope: w rows");
   TORCH_CHECK(positions.scalar_type() == at::kInt && slots.scalar_type() == at::kInt,
               "fused_qkv_rope: int32 positions/slots");
@@ -440,22 +468,24 @@ void fused_qkv_rope(at::Tensor q_out, at::Tensor k_cache, at::Tensor v_cache, co
                                x.data_ptr(), w.data_ptr(), positions.data_ptr<int>(),
                                slots.data_ptr<int>(), cos_sin.data_ptr<float>(), x.size(0),
                                x.size(1), x.stride(0), q_out.stride(0), n_q_heads, n_kv_heads,
-                               k_cache.size(2), static_cast<float>(eps), waves, ksplit, ws,
+                               k_cache.size(2), static_cast<float>(eps), waves, ksplit, ws, bs,
                                skinny_dtype(x, preshuffled), cur_stream()),
            "fused_qkv_rope");
 }
 
 void fused_gate_up_silu(at::Tensor out, const at::Tensor& x, const at::Tensor& w, double eps,
                         int64_t waves, bool preshuffled,
-                        const c10::optional<at::Tensor>& w_scale, int64_t ksplit) {
-  check_skinny(x, w, "fused_gate_up_silu");
-  const float* ws = fp8_scale(w, w_scale, "fused_gate_up_silu");
+                        const c10::optional<at::Tensor>& w_scale, int64_t ksplit,
+                        const c10::optional<at::Tensor>& w_block_scale) {
+  const uint8_t* bs = mxfp4_scale(x, w, w_scale, w_block_scale, "fused_gate_up_silu");
+  check_skinny(x, w, "fused_gate_up_silu", bs != nullptr);
+  const float* ws = bs != nullptr ? nullptr : fp8_scale(w, w_scale, "fused_gate_up_silu");
   TORCH_CHECK(w.size(0) == 2 * out.size(1) && out.size(0) == x.size(0) && out.stride(1) == 1,
               "fused_gate_up_silu: out");
   const at::DeviceGuard g(x.device());
   check_rc(atta_fused_gate_up_silu(out.data_ptr(), x.data_ptr(), w.data_ptr(), x.size(0),
                                    x.size(1), out.size(1), x.stride(0), out.stride(0),
-                                   static_cast<float>(eps), waves, ksplit, ws,
+                                   static_cast<float>(eps), waves, ksplit, ws, bs,
                                    skinny_dtype(x, preshuffled), cur_stream()),
            "fused_gate_up_silu");
 }
@@ -874,9 +904,11 @@ TORCH_LIBRARY(atta, m) {
   m.def(
       "fused_qkv_rope(Tensor(a!) q_out, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor x, "
       "Tensor w, Tensor positions, Tensor slots, Tensor cos_sin, int n_q_heads, int n_kv_heads, "
-      "float eps, int waves, bool preshuffled=False, Tensor? w_scale=None, int ksplit=1) -> ()");
+      "float eps, int waves, bool preshuffled=False, Tensor? w_scale=None, int ksplit=1, "
+      "Tensor? w_block_scale=None) -> ()");
   m.def("fused_gate_up_silu(Tensor(a!) out, Tensor x, Tensor w, float eps, int waves, "
-        "bool preshuffled=False, Tensor? w_scale=None, int ksplit=1) -> ()");
+        "bool preshuffled=False, Tensor? w_scale=None, int ksplit=1, "
+        "Tensor? w_block_scale=None) -> ()");
   m.def("set_splitk_workspace(Tensor ws, Tensor counters) -> ()");
   m.def("quant_rows_fp8(Tensor(a!) q, Tensor(b!) scale, Tensor x, Tensor? w, int mode, "
         "float eps, Tensor(c!)? residual=None) -> ()");
@@ -886,7 +918,8 @@ TORCH_LIBRARY(atta, m) {
       "int waves, bool preshuffled=False, Tensor? w_scale=None) -> ()");
   m.def("sample_finalize(Tensor(a!) tokens, Tensor keys, int n_tiles) -> ()");
   m.def("skinny_gemm(Tensor(a!) y, Tensor x, Tensor w, Tensor? residual, int waves, "
-        "bool preshuffled=False, Tensor? w_scale=None, int ksplit=1) -> ()");
+        "bool preshuffled=False, Tensor? w_scale=None, int ksplit=1, "
+        "Tensor? w_block_scale=None) -> ()");
   m.def("prefill_gemm(Tensor(a!) c, Tensor a, Tensor w, Tensor? residual, int mode, Tensor? xs=None, Tensor? ws=None, int schedule=-1, int bm=0) -> ()");
   m.def("prefill_gemm_auto_bm(int m) -> int", &prefill_gemm_auto_bm);
   m.def("prefill_gemm_error() -> int", &prefill_gemm_error);

@@ -239,9 +239,13 @@ void atta_get_wide_min_rows(int* m, int* m_silu) {
 //   fp8                   SAMPLE            > 32               None    those builds)
 //   any                   the push variant  1 - 32             Skinny (routes as row-major:
 //   any                   the push variant  > 32               None    the GEMV alone pushes)
+//   MXFP4 (pre-shuffled)  any but SAMPLE    1 - 32             Skinny (its W4 build,
+//   MXFP4                 any but SAMPLE    > 32               None    gemv_w4.hip)
+//   MXFP4                 SAMPLE, the push  any                None
 enum class Route { None, Skinny, Wide, MidM };
-static Route route(int M, bool ps, bool w8, int epi) {
+static Route route(int M, bool ps, bool w8, bool w4, int epi) {
   if (M < 1) return Route::None;
+  if (w4) return M <= kSkinnyMaxM && epi != EPI_SAMPLE ? Route::Skinny : Route::None;
   if (!ps) return M <= kSkinnyMaxM ? Route::Skinny : Route::None;
   const int wide_min = epi == EPI_SILU ? g_wide_min_m_silu : g_wide_min_m;
   if (M <= kSkinnyMaxM && (w8 || M < wide_min)) return Route::Skinny;
@@ -306,6 +310,21 @@ static int launch_skinny(SkinnyParams& p, int tiles, int waves, int ksplit, int 
   return static_cast<int>(hipGetLastError());
 }
 
+// The MXFP4 build of the 16-row-tile GEMV (gemv_w4.hip) for filled params; it fits the
+// split and the waves to K itself.
+int atta_w4_launch(SkinnyParams& p, int epi, int tiles, int waves, int ksplit, int dtype, bool nt,
+                   float* sk_ws, int* sk_counters, int64_t ws_floats, int n_counters,
+                   hipStream_t stream);
+static int launch_w4(SkinnyParams& p, int epi, int tiles, int waves, int ksplit, int dtype,
+                     hipStream_t stream) {
+  const SplitKWs* w = splitk_ws();
+  const SplitKWs none{};
+  if (w == nullptr) w = &none;
+  p.wg_trace = take_trace();
+  return atta_w4_launch(p, epi, tiles, waves, ksplit, dtype, nt_weights() != 0, w->ws,
+                        w->counters, w->ws_floats, w->n_counters, stream);
+}
+
 int atta_midm_launch(SkinnyParams& p, int epi, int ntiles, int dtype, float* sk_ws,
                      int64_t ws_floats, hipStream_t stream);
 // The wide small-M kernel (wide.hip) for filled params: the next-launch plan override and
@@ -334,8 +353,11 @@ static int launch_midm(SkinnyParams& p, int epi, int tiles, int dtype, hipStream
 template <int EPI>
 static int launch_routed(SkinnyParams& p, int tiles, int waves, int ksplit, int dtype,
                          hipStream_t stream) {
-  switch (route(p.M, p.ps != 0, p.wscale != nullptr, EPI)) {
-    case Route::Skinny: return launch_skinny<EPI>(p, tiles, waves, ksplit, dtype, stream);
+  if (p.bscale != nullptr && p.wscale != nullptr) return -1;
+  switch (route(p.M, p.ps != 0, p.wscale != nullptr, p.bscale != nullptr, EPI)) {
+    case Route::Skinny:
+      if (p.bscale != nullptr) return launch_w4(p, EPI, tiles, waves, ksplit, dtype, stream);
+      return launch_skinny<EPI>(p, tiles, waves, ksplit, dtype, stream);
     case Route::Wide: return launch_wide(p, EPI, tiles, dtype, stream);
     case Route::MidM: return launch_midm(p, EPI, tiles, dtype, stream);
     case Route::None: break;
@@ -345,7 +367,8 @@ static int launch_routed(SkinnyParams& p, int tiles, int waves, int ksplit, int 
 
 // The fields every entry point fills the same way.
 static SkinnyParams base_params(const void* x, const void* w, int M, int N, int K,
-                                int64_t x_stride, float eps, int ps, const float* wscale) {
+                                int64_t x_stride, float eps, int ps, const float* wscale,
+                                const uint8_t* bscale = nullptr) {
   SkinnyParams p{};
   p.x = static_cast<const uint16_t*>(x);
   p.w = static_cast<const uint16_t*>(w);
@@ -356,18 +379,20 @@ static SkinnyParams base_params(const void* x, const void* w, int M, int N, int 
   p.eps = eps;
   p.ps = ps;
   p.wscale = wscale;
+  p.bscale = bscale;
   return p;
 }
 
 int atta_skinny_gemm(void* y, const void* x, const void* w, const void* residual, int M, int N,
                      int K, int64_t x_stride, int64_t y_stride, int64_t res_stride, int waves,
-                     int ksplit, const float* wscale, int dtype, hipStream_t stream) {
+                     int ksplit, const float* wscale, const uint8_t* bscale, int dtype,
+                     hipStream_t stream) {
   const int ps = (dtype & kPreshuffled) ? 1 : 0;
   dtype &= ~kPreshuffled;
   // y := residual + x W^T is computed in place on the residual buffer: copy semantics are
   // not supported (callers pass y == residual)
   if (N % 16 != 0 || (residual != nullptr && residual != y)) return -1;
-  SkinnyParams p = base_params(x, w, M, N, K, x_stride, 0.f, ps, wscale);
+  SkinnyParams p = base_params(x, w, M, N, K, x_stride, 0.f, ps, wscale, bscale);
   p.y = static_cast<uint16_t*>(y);
   p.y_stride = residual != nullptr ? res_stride : y_stride;
   return residual != nullptr
@@ -386,7 +411,7 @@ int atta_skinny_gemm_push(const void* x, const void* w, int M, int N, int K, int
   dtype &= ~kPreshuffled;
   // only the 16-row-tile GEMV has the push epilogue: whatever the layout, the call routes
   // as row-major weights do
-  if (route(M, false, wscale != nullptr, EPI_PLAIN) != Route::Skinny || N % 16 != 0) return -1;
+  if (route(M, false, wscale != nullptr, false, EPI_PLAIN) != Route::Skinny || N % 16 != 0) return -1;
   if ((world != 2 && world != 4 && world != 8) || rank < 0 || rank >= world ||
       static_cast<int64_t>(M) * N > max_elems)
     return -1;
@@ -402,14 +427,14 @@ int atta_fused_qkv_rope(void* q_out, void* k_cache, void* v_cache, const void* x
                         const int* positions, const int* slots, const float* cos_sin, int M,
                         int K, int64_t x_stride, int64_t q_stride, int n_q_heads, int n_kv_heads,
                         int block_size, float eps, int waves, int ksplit, const float* wscale,
-                        int dtype, hipStream_t stream) {
+                        const uint8_t* bscale, int dtype, hipStream_t stream) {
   const int ps = (dtype & kPreshuffled) ? 1 : 0;
   dtype &= ~kPreshuffled;
   int shift = 0;
   while ((1 << shift) < block_size) ++shift;
   if ((1 << shift) != block_size) return -1;
   SkinnyParams p = base_params(x, w, M, (n_q_heads + 2 * n_kv_heads) * 128, K, x_stride, eps,
-                               ps, wscale);
+                               ps, wscale, bscale);
   p.y = static_cast<uint16_t*>(q_out);
   p.y_stride = q_stride;
   p.k_cache = static_cast<uint16_t*>(k_cache);
@@ -425,11 +450,12 @@ int atta_fused_qkv_rope(void* q_out, void* k_cache, void* v_cache, const void* x
 
 int atta_fused_gate_up_silu(void* out, const void* x, const void* w, int M, int K, int inter,
                             int64_t x_stride, int64_t out_stride, float eps, int waves,
-                            int ksplit, const float* wscale, int dtype, hipStream_t stream) {
+                            int ksplit, const float* wscale, const uint8_t* bscale, int dtype,
+                            hipStream_t stream) {
   const int ps = (dtype & kPreshuffled) ? 1 : 0;
   dtype &= ~kPreshuffled;
   if (inter % 8 != 0) return -1;
-  SkinnyParams p = base_params(x, w, M, 2 * inter, K, x_stride, eps, ps, wscale);
+  SkinnyParams p = base_params(x, w, M, 2 * inter, K, x_stride, eps, ps, wscale, bscale);
   p.y = static_cast<uint16_t*>(out);
   p.y_stride = out_stride;
   p.inter = inter;

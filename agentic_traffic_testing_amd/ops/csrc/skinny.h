@@ -111,6 +111,9 @@ struct SkinnyParams {
   uint8_t* push_base[arl::kMaxRanks];
   int push_world, push_rank;
   int64_t push_max_elems;
+  // MXFP4 weights (skinny_w4.h): w holds the pre-shuffled e2m1 codes and this the e8m0 block
+  // scales, 64 B per 16-row tile and 128-wide K chunk (one dword per row, byte j = K step j)
+  const uint8_t* bscale;
 };
 
 __device__ __forceinline__ unsigned ordered_bits(float f) {

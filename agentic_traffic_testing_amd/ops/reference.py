@@ -242,3 +242,40 @@ def rope_cos_sin(head_dim: int, max_pos: int, theta: float, scaling: dict | None
     t = torch.arange(max_pos, dtype=torch.float64)
     f = torch.outer(t, inv)
     return torch.cat([f.cos(), f.sin()], dim=-1).float().to(device)
+
+
+# ---- MXFP4 (OCP Microscaling FP4): e2m1 elements, one e8m0 scale per 32-element block -------
+MXFP4_BLOCK = 32
+E2M1_VALUES = (0.0, 0.5, 1.0, 1.5, 2.0, 3.0, 4.0, 6.0)  # magnitude of code & 7; bit 3 = sign
+
+
+def quantize_mxfp4(w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """[N, K] weight -> (e2m1 codes uint8 [N, K], one per byte; e8m0 scales uint8 [N, K / 32]).
+    Per block of 32 consecutive k: e = floor(log2(max|w|)) - 2 with b = e + 127 clamped to
+    [1, 254] (an all-zero block: b = 127); elements w / 2^e saturated to +-6 and rounded to
+    the nearest magnitude, ties to the even code; what rounds to zero is code 0, never -0.
+    Deterministic; runs on CPU and GPU tensors."""
+    N, K = w.shape
+    if K % MXFP4_BLOCK:
+        raise ValueError(f"mxfp4 needs K % {MXFP4_BLOCK} == 0, got {tuple(w.shape)}")
+    blk = w.float().reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    amax = blk.abs().amax(-1)
+    # amax = m * 2^ex with m in [0.5, 1): floor(log2(amax)) = ex - 1, exactly
+    e = torch.frexp(amax)[1].to(torch.int32) - 3
+    e = torch.where(amax > 0, e, torch.zeros_like(e)).clamp(1 - 127, 254 - 127)
+    a = torch.ldexp(blk.abs(), -e[..., None]).clamp(max=6.0)  # power-of-two scaling: exact
+    # nearest magnitude; a midpoint goes to the neighbour with the even code
+    idx = ((a > 0.25).to(torch.uint8) + (a >= 0.75) + (a > 1.25) + (a >= 1.75) + (a > 2.5)
+           + (a >= 3.5) + (a > 5.0))
+    codes = idx + (((blk < 0) & (idx > 0)).to(torch.uint8) << 3)
+    return codes.reshape(N, K), (e + 127).to(torch.uint8)
+
+
+def dequantize_mxfp4(codes: torch.Tensor, scales: torch.Tensor,
+                     dtype=torch.bfloat16) -> torch.Tensor:
+    """The values the codes stand for: +-magnitude * 2^(scale - 127), exact in bf16."""
+    N, K = codes.shape
+    mag = torch.tensor(E2M1_VALUES, dtype=torch.float32, device=codes.device)[(codes & 7).long()]
+    val = torch.where(codes >= 8, -mag, mag).reshape(N, K // MXFP4_BLOCK, MXFP4_BLOCK)
+    e = scales.to(torch.int32) - 127
+    return torch.ldexp(val, e[..., None]).reshape(N, K).to(dtype)
