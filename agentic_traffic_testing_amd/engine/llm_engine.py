@@ -38,6 +38,11 @@ class RequestOutput:
     first_scheduled_time: float | None = None
     finish_time: float | None = None
     new_token_ids: list = field(default_factory=list)
+    # SamplingParams.logprobs set: one entry per entry of token_ids (the first token, which
+    # comes out of the prefill step, included) - the token's logprob, and its position's
+    # [(token id, logprob), ...] alternatives, most likely first (empty lists for logprobs=0)
+    logprobs: list | None = None
+    top_logprobs: list | None = None
 
     @property
     def completion_tokens(self) -> int:
@@ -153,6 +158,7 @@ class LLMEngine:
     # ------------------------------------------------------------------------------------
     def add_request(self, request_id: str, prompt_ids, sampling: SamplingParams,
                     arrival_time: float | None = None) -> Sequence:
+        sampling.check()
         ids = list(map(int, prompt_ids))
         if not ids:
             ids = [self.tokenizer.bos_token_id]
@@ -251,17 +257,19 @@ class LLMEngine:
 
     def _collect(self, cur: "_Inflight") -> list[RequestOutput]:
         toks = self.runner.collect(cur.handle)
+        lps = self.runner.collect_logprobs(cur.handle)  # row i belongs to token i
         now = time.perf_counter()
         self.timing["execute"] += now - max(cur.t0, self._last_collect)
         self._last_collect = now
         self.timing["steps"] += 1
         outs = []
-        for (seq, idx, ncomp), tok in zip(cur.marks, toks):
+        for row, ((seq, idx, ncomp), tok) in enumerate(zip(cur.marks, toks)):
             if seq.status == SeqStatus.FINISHED:
                 continue  # aborted while in flight
             tok = int(tok)
             seq.output_ids[idx] = tok
             seq._ids_np = None
+            self._record_logprob(seq, idx, lps, row)
             if seq.first_token_time is None:
                 seq.first_token_time = now
             self.runner.bm.commit(seq.seq_id, seq.token_array(), ncomp)
@@ -275,6 +283,16 @@ class LLMEngine:
         self.timing["post"] += time.perf_counter() - now
         return outs
 
+    @staticmethod
+    def _record_logprob(seq: Sequence, idx: int, lps, row: int) -> None:
+        """Store row ``row`` of a step's logprob arrays as output token ``idx`` of a sequence
+        that asked for logprobs (a step runs the mode of its most demanding sequence; the
+        others get nothing)."""
+        if seq.logprobs is None:
+            return
+        lp, ids, vals = lps
+        seq.set_logprob(idx, lp[row], ((), ()) if ids is None else (ids[row], vals[row]))
+
     def _account(self, batch, n_out: int, seconds: float):
         self.total_steps += 1
         self.total_generated += n_out
@@ -286,17 +304,21 @@ class LLMEngine:
     def _sync_step(self, batch, t0: float) -> list[RequestOutput]:
         with self.lock:
             toks = self.runner.execute(batch)
+            lps = self.runner.last_logprobs
             now = time.perf_counter()
             self.timing["execute"] += now - t0
             self.timing["steps"] += 1
             outs = []
-            for seq, n, tok in zip(batch.seqs, batch.q_len, toks):
+            for row, (seq, n, tok) in enumerate(zip(batch.seqs, batch.q_len, toks)):
                 seq.num_computed += n
                 if seq.num_computed < seq.num_tokens:
                     self.runner.bm.commit(seq.seq_id, seq.token_array(), seq.num_computed)
                     continue  # chunked prefill not finished: sampled token discarded
                 tok = int(tok)
                 seq.append(tok)
+                # (a prefill recomputed after a preemption lands here too: one entry, for the
+                # one newly sampled token)
+                self._record_logprob(seq, len(seq.output_ids) - 1, lps, row)
                 if seq.first_token_time is None:
                     seq.first_token_time = now
                 self.runner.bm.commit(seq.seq_id, seq.token_array(), seq.num_computed)
@@ -322,6 +344,8 @@ class LLMEngine:
             return None
         if r.is_cuda and r._special(batch):
             return None  # a top-k / top-p row: the whole step samples through that kernel
+        if any(seq.sampling.logprobs is not None for seq in batch.seqs):
+            return None  # logprobs come from plain decode steps (verify rows record none)
         max_kv = r.verify_max_kv(S)
         if any(seq.num_tokens > max_kv for seq in batch.seqs):
             return None
@@ -401,7 +425,10 @@ class LLMEngine:
             finish_reason=seq.finish_reason, prompt_tokens=seq.num_prompt,
             cached_prompt_tokens=seq.num_cached_prompt, arrival_time=seq.arrival_time,
             first_token_time=seq.first_token_time, first_scheduled_time=seq.first_scheduled_time,
-            finish_time=seq.finish_time, new_token_ids=list(new))
+            finish_time=seq.finish_time, new_token_ids=list(new),
+            logprobs=None if seq.logprobs is None else list(seq.logprobs[:len(ids)]),
+            top_logprobs=(None if seq.top_logprobs is None
+                          else list(seq.top_logprobs[:len(ids)])))
 
     # ------------------------------------------------------------------------------------
     def generate(self, prompts, sampling: SamplingParams | list) -> list[RequestOutput]:

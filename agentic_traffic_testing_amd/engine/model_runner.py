@@ -105,6 +105,21 @@ class MetaLayout:
 HDR_WORDS = 12
 OP_STEP, OP_CAPTURE, OP_STOP, OP_BARRIER = 1, 2, 3, 4
 
+# step variant (header word 8, third part of a graph key, word 3 of OP_CAPTURE): bit 0 - some
+# row samples with top-k / top-p (logits materialised); bits 1-2 - the logprob mode of the
+# step's most demanding sequence
+V_TOPKP = 1
+LP_NONE, LP_SAMPLED, LP_TOPN = 0, 1, 2   # no logprobs / the sampled token's / + the top-N
+TOP_N = ops.MAX_TOP_LOGPROBS             # a top-N step computes this many; requests cut theirs
+
+
+def variant_code(topkp: bool, lp_mode: int) -> int:
+    return int(bool(topkp)) | (lp_mode << 1)
+
+
+def variant_lp(variant: int) -> int:
+    return variant >> 1
+
 
 class ModelRunner:
     def __init__(self, cfg: EngineConfig, model_cfg: ModelConfig, device: str = "cuda",
@@ -223,6 +238,15 @@ class ModelRunner:
         self.tok_host = [torch.zeros(max(cfg.max_num_seqs, self.ws_rows, 256), dtype=torch.int64,
                                      pin_memory=pin) for _ in range(2)]
         self._tok_done = [torch.cuda.Event() if self.is_cuda else None for _ in range(2)]
+        # logprobs of a step (SamplingParams.logprobs) ride the tokens' copy and event: one
+        # pinned buffer per token slot, laid out like the device buffer ws["lp_out"] -
+        # [lp: R | top ids: R x TOP_N (int32 bits) | top logprobs: R x TOP_N], R = lp_rows
+        self.lp_rows = max(cfg.max_num_seqs, self.ws_rows, self.max_seqs)
+        self.lp_host = [torch.zeros(self.lp_rows * (1 + 2 * TOP_N), dtype=torch.float32,
+                                    pin_memory=pin) for _ in range(2)]
+        # logprob arrays of the last execute() / verify()-free step: None, or (lp [n],
+        # top ids [n, TOP_N] | None, top logprobs [n, TOP_N] | None) as numpy
+        self.last_logprobs = None
         # the prefill GEMM's error word as of the last prefill step (0: every wait succeeded)
         self._err_host = torch.zeros(1, dtype=torch.int32, pin_memory=pin)
         # OR of the words read since the last take_kernel_error() (the device word is cleared
@@ -254,6 +278,18 @@ class ModelRunner:
             "max_parts": self.max_parts, "part_tokens": self.part_tokens,
         }
         del H
+        # logprob outputs (views of one buffer: one D2H copy moves them) and, where the fused
+        # LM head + sampler can record them (one GPU), its per-tile record workspace next to
+        # "keys": 16 B per key
+        R = self.lp_rows
+        lp_out = torch.zeros(R * (1 + 2 * TOP_N), dtype=torch.float32, device=dev)
+        self.ws.update({
+            "lp_out": lp_out, "lp": lp_out[:R],
+            "top_ids": lp_out[R:R + R * TOP_N].view(torch.int32).view(R, TOP_N),
+            "top_lp": lp_out[R + R * TOP_N:].view(R, TOP_N),
+            "lp_ws": (torch.zeros(4 * self.ws["keys"].numel(), dtype=torch.float32, device=dev)
+                      if self.is_cuda and self.tp_size == 1 else None),
+        })
         # the fused decode attention combines <= 64 partitions in-kernel (<= 16k tokens at
         # 256-token partitions); longer contexts use the two-kernel split-K path
         self.fused_decode = bool(cfg.fused_decode) and self.max_parts <= 64
@@ -429,11 +465,27 @@ class ModelRunner:
         need = max(1, math.ceil(max_kv / pt))
         return next((p for p in buckets if p >= need), top)
 
-    def _forward_sample(self, v: dict, md: AttnMeta, num_parts: int, special: bool = False):
-        """One step's forward + sampling; ``special``: some row uses top-p / top-k (logits
-        are materialised and the top-k / top-p kernel samples every row)."""
+    def _lp_fusable(self, variant: int) -> bool:
+        """Does this variant's logprob come out of the fused LM head + sampler (the SAMPLE_LP
+        epilogue)?  The sampled token's alone, no top-k / top-p row, one GPU; every other
+        logprob variant materialises the logits for ``ops.token_logprobs``."""
+        return variant == variant_code(False, LP_SAMPLED) and self.tp_size == 1
+
+    def _forward_sample(self, v: dict, md: AttnMeta, num_parts: int, variant: int = 0):
+        """One step's forward + sampling.  ``variant`` (variant_code): bit 0 - some row uses
+        top-p / top-k (logits are materialised and the top-k / top-p kernel samples every
+        row); bits 1-2 - the step's logprob mode, whose results land in ws["lp"] (and
+        ws["top_ids"] / ws["top_lp"]), one row per sampled row."""
         m = self.model
         T = v["input_ids"].shape[0]
+        special = bool(variant & V_TOPKP)
+        lp_mode = variant_lp(variant)
+        lp_fused = self._lp_fusable(variant)
+        # logits are materialised for top-k / top-p and for every logprob the fused sampler
+        # cannot record
+        mat = special or (lp_mode != LP_NONE and not lp_fused)
+        # alternatives a materialised logprob step computes (None: no logprobs)
+        lp_top = None if lp_mode == LP_NONE else (TOP_N if lp_mode == LP_TOPN else 0)
         if (self.fused_decode and md.num_tiles == 0
                 and md.num_decode == T and m.decode_step_fusable(T)):
             ws = self._ws_for(T)
@@ -443,7 +495,8 @@ class ModelRunner:
             return m.forward_decode(v["input_ids"], md, self.k_layers, self.v_layers,
                                     ws, v["temperature"], v["seeds"], v["steps"],
                                     prev_tokens=self.ws["tokens"], feed_prev=v["feed_prev"],
-                                    top_p=v["top_p"] if special else None, top_k=v["top_k"])
+                                    top_p=v["top_p"] if special else None, top_k=v["top_k"],
+                                    lp_top=lp_top, lp_fused=lp_fused)
         decode_only = md.num_tiles == 0 and md.num_decode == T
         # final norm on the sampled rows only (each sequence's last token)
         last = m.forward(v["input_ids"], md, self.k_layers, self.v_layers, self.part_out,
@@ -451,29 +504,35 @@ class ModelRunner:
                          prev_tokens=self.ws["tokens"] if decode_only else None,
                          feed_prev=v["feed_prev"] if decode_only else None,
                          rows=v["logits_idx"])
-        if not special and m.sampler_fusable(last.shape[0]) and last.shape[0] <= self.max_seqs:
+        if not mat and m.sampler_fusable(last.shape[0]) and last.shape[0] <= self.max_seqs:
             # fused LM head + Gumbel-max sampler on the (already normalised) last rows
-            return m.sample_rows(last, 0.0, v["temperature"], v["seeds"], v["steps"], self.ws)
+            return m.sample_rows(last, 0.0, v["temperature"], v["seeds"], v["steps"], self.ws,
+                                 logprobs=lp_fused)
         logits = m.compute_logits(last)
         # decode-only steps sample straight into ws["tokens"]: a graph replay (and the next
         # look-ahead step's embed) reads the samples from there, so the captured sampler must
         # write them there too (a fresh tensor would leave the previous step's tokens behind)
         out = self.ws["tokens"][:logits.shape[0]] if decode_only else None
         if special:
-            return ops.sample_topkp(logits, v["temperature"], v["top_p"], v["top_k"],
+            toks = ops.sample_topkp(logits, v["temperature"], v["top_p"], v["top_k"],
                                     v["seeds"], v["steps"], out=out)
-        return ops.sample(logits, v["temperature"], v["seeds"], v["steps"], out=out)
+        else:
+            toks = ops.sample(logits, v["temperature"], v["seeds"], v["steps"], out=out)
+        if lp_top is not None:
+            m.logits_logprobs(logits, toks, lp_top, self.ws)
+        return toks
 
     # ------------------------------------------------------------------------------------
-    def _graph_ok(self, bucket: int, special: bool = False) -> bool:
+    def _graph_ok(self, bucket: int, variant: int = 0) -> bool:
         """Can a decode step of this bucket be captured?  Every collective inside it must be
         device-side: RCCL, or - on a gloo control group (TP ranks rehearsing on one GPU) - the
         IPC kernels, which carry the fused decode step's X1/X2 sums and X4 key MAX but not the
-        logits all-gather of the top-k / top-p sampler or of buckets past the fused path."""
+        logits all-gather of the top-k / top-p sampler, of a logprob variant (every one
+        materialises its logits under TP) or of buckets past the fused path."""
         c = self.comm
         if c is None or c.size == 1 or not c.is_gloo:
             return True
-        return (c.decode_capturable and not special and self.fused_decode
+        return (c.decode_capturable and variant == 0 and self.fused_decode
                 and self.model.decode_step_fusable(bucket))
 
     def graph_bucket(self, batch: Batch) -> int:
@@ -483,20 +542,47 @@ class ModelRunner:
                 and self.graph_sizes and n <= self.graph_sizes[-1]):
             return 0
         b = next(b for b in self.graph_sizes if b >= n)
-        return b if self._graph_ok(b, self._special(batch)) else 0
+        return b if self._graph_ok(b, self._variant(batch)) else 0
 
     @staticmethod
     def _special(batch: Batch) -> bool:
         return any(s.sampling.top_p < 1.0 or s.sampling.top_k > 0 for s in batch.seqs)
 
+    @staticmethod
+    def _lp_mode(batch: Batch) -> int:
+        """Logprob mode of a step: that of its most demanding sequence (the others' results
+        are dropped by the engine)."""
+        want = [s.sampling.logprobs for s in batch.seqs if s.sampling.logprobs is not None]
+        if not want:
+            return LP_NONE
+        return LP_TOPN if max(want) > 0 else LP_SAMPLED
+
+    @classmethod
+    def _variant(cls, batch: Batch) -> int:
+        return variant_code(cls._special(batch), cls._lp_mode(batch))
+
+    def _fetch_logprobs(self, variant: int, n: int):
+        """Synchronous copy of a step's logprob arrays (eager steps, after the tokens')."""
+        mode = variant_lp(variant)
+        if mode == LP_NONE:
+            return None
+        lp = self.ws["lp"][:n].cpu().numpy()
+        if mode != LP_TOPN:
+            return lp, None, None
+        return lp, self.ws["top_ids"][:n].cpu().numpy(), self.ws["top_lp"][:n].cpu().numpy()
+
     def execute(self, batch: Batch) -> np.ndarray:
-        """Run one step; returns sampled token ids (one per sequence in batch order)."""
+        """Run one step; returns sampled token ids (one per sequence in batch order).  A
+        step in which a sequence asked for logprobs leaves them in ``last_logprobs``."""
         n = len(batch.seqs)
         bucket = self.graph_bucket(batch)
         if bucket:
-            return self.collect(self.launch(batch))
+            h = self.launch(batch)
+            toks = self.collect(h)
+            self.last_logprobs = self.collect_logprobs(h)
+            return toks
         self.steps += 1
-        special = self._special(batch)
+        variant = self._variant(batch)
         lay, arrays = self._prepare(batch)
         max_kv = int(arrays["seq_kvlen"][:batch.num_decode].max()) if batch.num_decode else 0
         if batch.num_decode == n and lay.NT == 0:
@@ -507,7 +593,7 @@ class ModelRunner:
             num_parts = max(1, math.ceil(max_kv / self.part_tokens))
         host = self._pack(lay, arrays)
         hdr = np.array([OP_STEP, lay.T, lay.S, lay.W, lay.NT, batch.num_decode, num_parts,
-                        0, int(special), n, lay.size, 0], dtype=np.int32)
+                        0, variant, n, lay.size, 0], dtype=np.int32)
         if self.publisher is not None:
             self.publisher.publish(np.concatenate([hdr, host]))
         toks = self._run(hdr)
@@ -518,6 +604,7 @@ class ModelRunner:
             self._err_host.zero_()
             ops.prefill_gemm_error_to(self._err_host, clear=True)
         out = toks[:n].cpu().numpy()
+        self.last_logprobs = self._fetch_logprobs(variant, n)
         word = int(self._err_host[0]) if self.is_cuda else 0
         if word:
             self._err_host.zero_()
@@ -652,23 +739,23 @@ class ModelRunner:
             raise ValueError("launch() needs a decode-only batch")
         n = len(batch.seqs)
         bucket = self.graph_bucket(batch)
-        special = int(self._special(batch))
+        variant = self._variant(batch)
         self.steps += 1
         t0 = time.perf_counter()
         if bucket:
             lay, arrays = self._prepare(batch, pad_seqs=bucket, tiles=False)
             num_parts = self.parts_bucket(int(arrays["seq_kvlen"][:n].max()), bucket)
-            if (bucket, num_parts, special) not in self.graphs:
-                self.capture(bucket, num_parts, bool(special))
+            if (bucket, num_parts, variant) not in self.graphs:
+                self.capture(bucket, num_parts, variant)
                 t0 = time.perf_counter()
-            assert lay.size == self.graph_io[(bucket, num_parts, special)]["layout"].size
+            assert lay.size == self.graph_io[(bucket, num_parts, variant)]["layout"].size
         else:
             lay, arrays = self._prepare(batch, tiles=False)
             num_parts = self.parts_bucket(int(arrays["seq_kvlen"][:n].max()), n)
         arrays["feed_prev"] = np.array([1 if lookahead else 0], dtype=np.int32)
         host = self._pack(lay, arrays)
         hdr = np.array([OP_STEP, lay.T, lay.S, lay.W, lay.NT, batch.num_decode, num_parts,
-                        bucket, special, n, lay.size, 0], dtype=np.int32)
+                        bucket, variant, n, lay.size, 0], dtype=np.int32)
         if self.publisher is not None:
             self.publisher.publish(np.concatenate([hdr, host]))
         t1 = time.perf_counter()
@@ -679,11 +766,17 @@ class ModelRunner:
         if ev is not None:
             ev.synchronize()
         self.tok_host[slot][:n].copy_(dev_toks[:n], non_blocking=self.is_cuda)
+        lp_mode = variant_lp(variant)
+        if lp_mode != LP_NONE:
+            # the logprobs ride the same event: the sampled tokens' alone are the head of the
+            # buffer, a top-N step moves all of it
+            k = n if lp_mode == LP_SAMPLED else self.lp_host[slot].numel()
+            self.lp_host[slot][:k].copy_(self.ws["lp_out"][:k], non_blocking=self.is_cuda)
         if ev is not None:
             ev.record()
         if bucket:
             self.timing["graph_prep"] += t1 - t0
-        return {"n": n, "slot": slot, "t_launch": t1, "graph": bool(bucket)}
+        return {"n": n, "slot": slot, "t_launch": t1, "graph": bool(bucket), "lp_mode": lp_mode}
 
     def collect(self, h: dict) -> np.ndarray:
         """Wait for a launched step's tokens."""
@@ -698,9 +791,22 @@ class ModelRunner:
         self._last_collect = now
         return self.tok_host[h["slot"]][:h["n"]].numpy().copy()
 
+    def collect_logprobs(self, h: dict):
+        """Logprob arrays of a collected step (call after ``collect``): None, or (lp [n], top
+        ids [n, TOP_N] | None, top logprobs [n, TOP_N] | None) - row i belongs to token i."""
+        mode, n, R = h.get("lp_mode", LP_NONE), h["n"], self.lp_rows
+        if mode == LP_NONE:
+            return None
+        host = self.lp_host[h["slot"]].numpy()
+        lp = host[:n].copy()
+        if mode != LP_TOPN:
+            return lp, None, None
+        ids = host[R:R + R * TOP_N].view(np.int32).reshape(R, TOP_N)[:n].copy()
+        return lp, ids, host[R + R * TOP_N:].reshape(R, TOP_N)[:n].copy()
+
     def _run(self, hdr):
         """Execute one step from its header; the packed metadata is in ``meta_host``."""
-        T, S, W, NT, num_decode, num_parts, bucket, special, n, size = (int(x) for x in hdr[1:11])
+        T, S, W, NT, num_decode, num_parts, bucket, variant, n, size = (int(x) for x in hdr[1:11])
         if int(hdr[11]):  # verify step: row-sized sampling fields, multi-query attention
             lay = MetaLayout(T, S, W, NT, T)
             dev = self.meta_dev[:size]
@@ -709,7 +815,7 @@ class ModelRunner:
             return self._forward_verify(v, self._meta(v, num_decode, NT), num_parts,
                                         int(hdr[11]) & 0xFF, int(hdr[11]) >> 8)
         if bucket:
-            key = (bucket, num_parts, special)
+            key = (bucket, num_parts, variant)
             io = self.graph_io[key]
             self._h2d(io["dev"], size)
             self.graphs[key].replay()
@@ -721,7 +827,7 @@ class ModelRunner:
         v = lay.views(dev)
         md = self._meta(v, num_decode, NT)
         # every rank samples (deterministic kernels over all-gathered logits under TP)
-        out = self._forward_sample(v, md, num_parts, bool(special))
+        out = self._forward_sample(v, md, num_parts, variant)
         if NT == 0 and num_decode == T and out is not None:
             # every rank keeps the decode samples where a look-ahead step embeds them from
             dev_toks = self.ws["tokens"]
@@ -753,7 +859,7 @@ class ModelRunner:
             if op == OP_STOP:
                 return
             if op == OP_CAPTURE:
-                self.capture(int(hdr[1]), int(hdr[2]) or None, bool(hdr[3]))
+                self.capture(int(hdr[1]), int(hdr[2]) or None, int(hdr[3]))
                 continue
             if op == OP_BARRIER:
                 if self.is_cuda:
@@ -788,14 +894,16 @@ class ModelRunner:
                 self.publisher.close()
 
     # ------------------------------------------------------------------------------------
-    def capture(self, bucket: int, parts: int | None = None, special: bool = False):
+    def capture(self, bucket: int, parts: int | None = None, variant: int = 0):
         """Capture a decode step for `bucket` sequences whose contexts fit `parts` attention
-        partitions (default: max_model_len) into a hipGraph; ``special``: the top-k / top-p
-        sampler variant (logits materialised)."""
+        partitions (default: max_model_len) into a hipGraph; ``variant`` (variant_code): the
+        top-k / top-p sampler (logits materialised) and / or a logprob mode.  Variants other
+        than 0 are captured on first use."""
+        variant = int(variant)
         parts = parts or self._tier(bucket)[1]
         if self.publisher is not None:
             hdr = np.zeros(HDR_WORDS, dtype=np.int32)
-            hdr[0], hdr[1], hdr[2], hdr[3] = OP_CAPTURE, bucket, parts, int(special)
+            hdr[0], hdr[1], hdr[2], hdr[3] = OP_CAPTURE, bucket, parts, variant
             self.publisher.publish(hdr)
         lay = MetaLayout(bucket, bucket, self.bt_width, 0)
         dev = torch.zeros(lay.size, dtype=torch.int32, device=self.device)
@@ -813,7 +921,7 @@ class ModelRunner:
         stream.wait_stream(torch.cuda.current_stream(self.device))
         with torch.cuda.stream(stream):
             for _ in range(2):  # warm up (hipBLASLt heuristics, allocator)
-                self._forward_sample(v, md, parts, special)
+                self._forward_sample(v, md, parts, variant)
         torch.cuda.current_stream(self.device).wait_stream(stream)
         dump_dir = os.environ.get("ATTA_GRAPH_DUMP_DIR")
         # node-level dump of every captured step (scripts/gpu/graph_nodes.py) keeps the
@@ -822,19 +930,19 @@ class ModelRunner:
         if self.graph_pool is None:
             self.graph_pool = torch.cuda.graph_pool_handle()
         with torch.cuda.graph(g, pool=self.graph_pool, stream=stream):
-            out = self._forward_sample(v, md, parts, special)
+            out = self._forward_sample(v, md, parts, variant)
             toks = self.ws["tokens"]
             if out.data_ptr() != toks.data_ptr():  # every sampler path ends in ws["tokens"]
                 toks[:bucket].copy_(out[:bucket])
                 out = toks[:bucket]
         self.ws["tokens"].copy_(saved_tokens)
         torch.cuda.synchronize(self.device)
-        key = (bucket, parts, int(special))
+        key = (bucket, parts, variant)
         if dump_dir:
             os.makedirs(dump_dir, exist_ok=True)
             nodes = ops._native().graph_nodes(int(g.raw_cuda_graph()))
             path = os.path.join(dump_dir, f"tp{self.tp_size}_rank{self.tp_rank}_b{bucket}"
-                                          f"_p{parts}_s{int(special)}.nodes")
+                                          f"_p{parts}_s{variant}.nodes")
             with open(path, "w") as f:
                 f.write("\n".join(nodes) + "\n")
         self.graphs[key] = g
@@ -899,4 +1007,5 @@ class ModelRunner:
 
 
 __all__ = ["ModelRunner", "MetaLayout", "ref", "HDR_WORDS", "OP_STEP", "OP_CAPTURE", "OP_STOP",
-           "OP_BARRIER"]
+           "OP_BARRIER", "LP_NONE", "LP_SAMPLED", "LP_TOPN", "TOP_N", "variant_code",
+           "variant_lp"]

@@ -9,6 +9,9 @@ from dataclasses import dataclass, field
 import numpy as np
 
 
+MAX_LOGPROBS = 20  # most alternatives per position (ops.MAX_TOP_LOGPROBS)
+
+
 @dataclass
 class SamplingParams:
     """Per-request sampling knobs.  The reference sends SamplingParams(temperature=0.2,
@@ -21,6 +24,21 @@ class SamplingParams:
     stop_token_ids: tuple = ()
     top_p: float = 1.0
     top_k: int = -1
+    # None: no logprobs; 0: the logprob of each sampled token; N in 1 .. 20: also the N most
+    # likely tokens of each position (higher logit first, equal logits by lower id).  A logprob
+    # is l_tok - logsumexp(l) in fp32 over the RAW logits the sampler sees - the LM-head product
+    # rounded to the model dtype, before temperature, Gumbel noise and top-k / top-p (vLLM's
+    # default "raw_logprobs").  Tokens do not depend on this field.
+    logprobs: int | None = None
+
+    def check(self) -> None:
+        """Raise ValueError for a field the engine cannot serve (called when a request is
+        added)."""
+        lp = self.logprobs
+        if lp is not None and (isinstance(lp, bool) or not isinstance(lp, int)
+                               or not 0 <= lp <= MAX_LOGPROBS):
+            raise ValueError(f"logprobs must be None or an integer in 0 .. {MAX_LOGPROBS}, "
+                             f"got {lp!r}")
 
 
 class SeqStatus(enum.Enum):
@@ -49,6 +67,10 @@ class Sequence:
     finish_reason: str | None = None
     seed: int = 0
     num_preemptions: int = 0
+    # with sampling.logprobs set: one entry per entry of output_ids - the token's logprob, and
+    # (logprobs >= 1) the position's [(id, logprob), ...] alternatives
+    logprobs: list | None = None
+    top_logprobs: list | None = None
     _ids_np: np.ndarray | None = None
 
     @property
@@ -77,6 +99,23 @@ class Sequence:
             self._ids_np = a
         return a
 
+    def __post_init__(self):
+        if self.sampling.logprobs is not None:
+            self.logprobs = []
+            self.top_logprobs = []
+
     def append(self, tok: int):
         self.output_ids.append(int(tok))
         self._ids_np = None
+
+    def set_logprob(self, idx: int, lp: float, top) -> None:
+        """Record output token ``idx``'s logprob and alternatives (ids, logprobs arrays; cut
+        to the N this request asked for).  Positions are filled in order; ``idx`` below the
+        length overwrites (a look-ahead placeholder's slot)."""
+        if self.logprobs is None:
+            return
+        n = self.sampling.logprobs
+        alts = [(int(i), float(v)) for i, v in zip(top[0][:n], top[1][:n])] if n else []
+        del self.logprobs[idx:], self.top_logprobs[idx:]
+        self.logprobs.append(float(lp))
+        self.top_logprobs.append(alts)

@@ -548,7 +548,8 @@ class LlamaModel:
     def forward_decode(self, input_ids: torch.Tensor, md: AttnMeta, k_caches, v_caches, ws: dict,
                        temperature, seeds, steps, prev_tokens=None,
                        feed_prev=None, top_p=None, top_k=None, max_qlen: int = 1,
-                       min_qlen: int = 1) -> torch.Tensor:
+                       min_qlen: int = 1, lp_top: int | None = None,
+                       lp_fused: bool = False) -> torch.Tensor:
         """Fused decode step; returns sampled ids, one per row.  Every sequence has one query
         row - or, in a verify step of speculative decoding (``max_qlen`` > 1: the longest of
         the batch), sequence s of ``md.num_decode`` has the rows ``md.seq_qstart[s]`` ..
@@ -562,7 +563,13 @@ class LlamaModel:
         [down_proj + residual add]; then [final RMSNorm + LM head + sampler].  5 kernels per
         layer instead of ~10, no normalised activations or logits ever hit HBM.  With
         ``top_p`` / ``top_k`` (per-row device tensors) the step ends in final RMSNorm + LM head
-        + the top-k / top-p sampler kernel instead (logits materialised)."""
+        + the top-k / top-p sampler kernel instead (logits materialised).
+
+        ``lp_top`` (None: off): the step also leaves each row's sampled-token logprob in
+        ws["lp"] - with ``lp_fused`` from the fused LM head + sampler's logprob epilogue (same
+        launch count, tokens bit-identical to the plain step's), else from the materialised
+        logits through ``ops.token_logprobs`` with its ``lp_top`` alternatives in
+        ws["top_ids"] / ws["top_lp"]."""
         eps = self.cfg.rms_norm_eps
         nq, nkv = self.n_heads, self.n_kv_heads
         B = input_ids.shape[0]
@@ -596,11 +603,27 @@ class LlamaModel:
             ops.decode_gate_up_silu(residual, eps=eps, out=act,
                                     **self._decode_w(L, "gate_up", B))
             self._row_parallel(act, L, "down", residual)
-        if top_p is not None:
+        if top_p is not None or (lp_top is not None and not lp_fused):
             logits = self.compute_logits(ops.rms_norm(residual, self.norm, eps))
-            return ops.sample_topkp(logits, temperature, top_p, top_k, seeds, steps,
-                                    out=ws["tokens"][:B])
-        return self.sample_rows(residual, eps, temperature, seeds, steps, ws)
+            if top_p is not None:
+                toks = ops.sample_topkp(logits, temperature, top_p, top_k, seeds, steps,
+                                        out=ws["tokens"][:B])
+            else:
+                toks = ops.sample(logits, temperature, seeds, steps, out=ws["tokens"][:B])
+            if lp_top is not None:
+                self.logits_logprobs(logits, toks, lp_top, ws)
+            return toks
+        return self.sample_rows(residual, eps, temperature, seeds, steps, ws,
+                                logprobs=lp_top is not None)
+
+    @staticmethod
+    def logits_logprobs(logits: torch.Tensor, toks: torch.Tensor, n_top: int, ws: dict) -> None:
+        """Logprobs of the samples ``toks`` under the materialised ``logits`` rows, and the
+        ``n_top`` most likely tokens per row, into ws["lp"] / ws["top_ids"] / ws["top_lp"]
+        (every rank under TP: the logits are all-gathered)."""
+        n = logits.shape[0]
+        ops.token_logprobs(logits, toks, n_top,
+                           out=(ws["lp"][:n], ws["top_ids"][:n], ws["top_lp"][:n]))
 
     def _row_parallel(self, x: torch.Tensor, L, proj: str, residual: torch.Tensor) -> None:
         """residual += x @ W.T for the row-parallel o / down projection on the fused kernels
@@ -629,18 +652,23 @@ class LlamaModel:
                 ops.linear(x, w, waves=waves, preshuffled=ps, w_scale=scale, ksplit=None,
                            proj=proj), residual)
 
-    def sample_rows(self, x, eps, temperature, seeds, steps, ws) -> torch.Tensor:
+    def sample_rows(self, x, eps, temperature, seeds, steps, ws,
+                    logprobs: bool = False) -> torch.Tensor:
         """[final RMSNorm (eps > 0) +] LM head + sampler for ``sampler_fusable`` rows (<= 32 on
         row-major weights, <= 128 pre-shuffled) without materialising logits; tokens land in
         ws["tokens"][:B] on every rank (an async look-ahead step embeds them from there).  Used
         by the fused decode step and for the last-token rows of prefill steps (their rows are
-        already normalised: eps = 0)."""
+        already normalised: eps = 0).  ``logprobs`` (one GPU only): the launch records each
+        token's logprob into ws["lp"][:B] as well (the SAMPLE_LP epilogue)."""
         B = x.shape[0]
         lm_ps = self.lm_head_ps is not None
         lm = self.lm_head_ps if lm_ps else self.lm_head
         if self.tp_size == 1:
+            lp = {"logprobs": ws["lp"][:B], "lp_ws": ws["lp_ws"]} if logprobs else {}
             return ops.decode_lm_head_sample(x, lm, eps, temperature, seeds, steps, ws["keys"],
-                                             tokens=ws["tokens"][:B], preshuffled=lm_ps)
+                                             tokens=ws["tokens"][:B], preshuffled=lm_ps, **lp)
+        if logprobs:
+            raise RuntimeError("sample_rows: vocab-parallel shards have no logprob epilogue")
         # TP: each rank samples its vocab shard down to one packed key per row (global ids,
         # so the Gumbel noise equals TP=1's); one int64 MAX all-reduce picks the winner
         keys = ops.decode_lm_head_sample(x, lm, eps, temperature, seeds, steps, ws["keys"],

@@ -413,14 +413,18 @@ def _policy_tops() -> tuple[int, int, int]:
 def fused_kernel(m: int, preshuffled: bool, fp8: bool = False, epi: str = "plain",
                  mxfp4: bool = False) -> str | None:
     """Which hand-written weight-streaming kernel runs ``m`` rows over this weight layout with
-    this epilogue ("plain" | "resadd" | "qkv" | "silu" | "sample" | "push"): "skinny" (the
+    this epilogue ("plain" | "resadd" | "qkv" | "silu" | "sample" | "sample_lp" | "push";
+    "sample_lp", the sampler with the logprob record, routes as "sample" does but has no fp8
+    build): "skinny" (the
     16-row-tile GEMV), "wide", "midm", or None (no kernel: the native call would fail).  The
     routing table of csrc/gemv.hip ``route()`` (written out there and in docs/kernels.md)
     under the policy limits above.  ``mxfp4``: the 4-bit copies (``preshuffle_mxfp4``), which
     only the 16-row-tile GEMV streams.  Pure: no native call, usable without a GPU."""
     skinny_top, wide_top, midm_top = _policy_tops()
-    if m < 1:
+    if m < 1 or (epi == "sample_lp" and fp8):
         return None
+    if epi == "sample_lp":
+        epi = "sample"
     if mxfp4:
         return "skinny" if m <= skinny_top and epi not in ("sample", "push") else None
     if not (preshuffled or fp8) or epi == "push" or not wide_top:
@@ -1012,18 +1016,70 @@ def decode_gate_up_silu(x, w, eps, out=None, preshuffled=False, w_scale=None, ks
     return out
 
 
+MAX_TOP_LOGPROBS = 20  # most alternatives per position (csrc/logprobs.hip, SamplingParams)
+
+
+def token_logprobs(logits, tokens, n_top: int = 0, out=None):
+    """Logprobs of ``tokens`` (int64, one per row) under the raw ``logits`` rows (bf16 / fp32:
+    before temperature, noise and top-k / top-p), in fp32, and the ``n_top`` (0 .. 20) most
+    likely ids of each row with theirs - higher logit first, equal logits by lower id
+    (csrc/logprobs.hip: one workgroup per row; ids and logits are read on the device and
+    ``n_top`` is fixed per call, so the launch is graph-capturable).  Returns (lp [rows] fp32,
+    top_ids [rows, n_top] int32, top_lp [rows, n_top] fp32); ``out``: that triple to fill."""
+    rows = logits.shape[0]
+    if not 0 <= n_top <= MAX_TOP_LOGPROBS:
+        raise ValueError(f"token_logprobs: n_top {n_top} not in 0 .. {MAX_TOP_LOGPROBS}")
+    if not logits.is_cuda:
+        r = ref.token_logprobs(logits, tokens, n_top)
+        if out is not None:
+            for o, v in zip(out, r):
+                o.view(-1)[:v.numel()].copy_(v.reshape(-1))
+            return tuple(o.view(-1)[:v.numel()].view(v.shape) for o, v in zip(out, r))
+        return r
+    if out is None:
+        out = (torch.empty(rows, dtype=torch.float32, device=logits.device),
+               torch.empty(rows, n_top, dtype=torch.int32, device=logits.device),
+               torch.empty(rows, n_top, dtype=torch.float32, device=logits.device))
+    lp, top_ids, top_lp = out
+    _native().token_logprobs(lp, top_ids, top_lp, logits, tokens, n_top)
+    return (lp.view(-1)[:rows], top_ids.view(-1)[:rows * n_top].view(rows, n_top),
+            top_lp.view(-1)[:rows * n_top].view(rows, n_top))
+
+
 def decode_lm_head_sample(x, w, eps, temperature, seeds, steps, keys, tokens=None,
-                          finalize=True, vocab_offset=0, preshuffled=False):
+                          finalize=True, vocab_offset=0, preshuffled=False, logprobs=None,
+                          lp_ws=None):
     """Final RMSNorm -> LM head -> greedy / Gumbel-max sample without materialising logits.
     ``keys`` (int64, >= M * vocab/16 entries) is scratch for the per-tile packed
     (value, index) maxima; no initialisation is needed.
 
     ``finalize``: True -> ``tokens`` gets token ids; ``"key"`` -> ``tokens`` gets each row's
     signed-orderable packed key (TP: MAX all-reduce them, then ``key_to_token``); False ->
-    partials only.  ``vocab_offset`` is this shard's first vocab id."""
+    partials only.  ``vocab_offset`` is this shard's first vocab id.
+
+    ``logprobs`` (fp32, >= M entries): also filled with each sampled token's logprob,
+    ``l_tok - logsumexp(l)`` in fp32 over the raw logits the sampler sees (the LM-head product
+    rounded to the model dtype, before temperature and noise) - the SAMPLE_LP epilogue, whose
+    keys and tokens are bit-identical to the plain launch's.  Needs ``lp_ws``, fp32 scratch of
+    4 words per ``keys`` entry, ``finalize=True`` and a whole vocabulary (``vocab_offset`` 0);
+    16-bit weights only."""
     _need_cuda(x, preshuffled)
     if tokens is None:
         tokens = torch.empty(x.shape[0], dtype=torch.long, device=x.device)
+    if logprobs is not None:
+        if finalize is not True or vocab_offset != 0:
+            raise ValueError("decode_lm_head_sample: logprobs need finalize=True on one shard")
+        if not x.is_cuda:
+            t, lp = ref.lm_head_sample_logprobs(x, w, eps, temperature, seeds, steps)
+            tokens.copy_(t)
+            logprobs[:lp.shape[0]].copy_(lp)
+            return tokens
+        if lp_ws is None:
+            raise ValueError("decode_lm_head_sample: logprobs need the lp_ws workspace")
+        _native().fused_lm_head_sample_lp(tokens, logprobs, keys, lp_ws, x, w, eps, temperature,
+                                          seeds, steps, decode_waves("lm_head", preshuffled),
+                                          preshuffled)
+        return tokens
     if not x.is_cuda:
         n = ref.rms_norm(x, torch.ones(x.shape[1], dtype=x.dtype), eps)
         logits = torch.nn.functional.linear(n, w)

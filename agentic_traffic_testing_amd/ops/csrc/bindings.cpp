@@ -277,6 +277,36 @@ void sample_topkp(at::Tensor out, const at::Tensor& logits, const at::Tensor& te
            "sample_topkp");
 }
 
+void token_logprobs(at::Tensor lp, at::Tensor top_ids, at::Tensor top_lp,
+                    const at::Tensor& logits, const at::Tensor& tokens, int64_t n_top) {
+  check_dev(logits, "logits");
+  TORCH_CHECK(lp.scalar_type() == at::kFloat && top_ids.scalar_type() == at::kInt &&
+                  top_lp.scalar_type() == at::kFloat && tokens.scalar_type() == at::kLong,
+              "token_logprobs: dtypes");
+  TORCH_CHECK(logits.dim() == 2 && logits.stride(1) == 1, "token_logprobs: logits 2-D");
+  const int64_t rows = logits.size(0);
+  TORCH_CHECK(n_top >= 0 && n_top <= 20, "token_logprobs: n_top in 0 .. 20");
+  TORCH_CHECK(logits.size(1) > 0 && logits.size(1) < (int64_t{1} << 31),
+              "token_logprobs: vocab");
+  TORCH_CHECK(lp.is_contiguous() && top_ids.is_contiguous() && top_lp.is_contiguous() &&
+                  tokens.is_contiguous() && lp.numel() >= rows && tokens.numel() >= rows &&
+                  top_ids.numel() >= rows * n_top && top_lp.numel() >= rows * n_top,
+              "token_logprobs: per-row arrays");
+  TORCH_CHECK(lp.device() == logits.device() && top_ids.device() == logits.device() &&
+                  top_lp.device() == logits.device() && tokens.device() == logits.device(),
+              "token_logprobs: one device");
+  const bool is_f32 = logits.scalar_type() == at::kFloat;
+  TORCH_CHECK(is_f32 || logits.scalar_type() == at::kBFloat16,
+              "token_logprobs: logits fp32/bf16");
+  const at::DeviceGuard g(logits.device());
+  check_rc(atta_token_logprobs(lp.data_ptr<float>(), top_ids.data_ptr<int>(),
+                               top_lp.data_ptr<float>(), logits.data_ptr(),
+                               tokens.data_ptr<int64_t>(), rows, logits.size(1),
+                               logits.stride(0), is_f32 ? 1 : 0, static_cast<int>(n_top),
+                               cur_stream()),
+           "token_logprobs");
+}
+
 // fp8 weight-only quantisation: w is uint8 (OCP e4m3fn bytes, pre-shuffled in 16 x 64 blocks)
 // and w_scale the fp32 per-row dequant scale; returns the scale pointer (nullptr: 16-bit w).
 const float* fp8_scale(const at::Tensor& w, const c10::optional<at::Tensor>& w_scale,
@@ -513,6 +543,39 @@ void fused_lm_head_sample(at::Tensor tokens, at::Tensor keys, const at::Tensor& 
                static_cast<int>(finalize), static_cast<int>(vocab_offset), waves, ws,
                skinny_dtype(x, preshuffled), cur_stream()),
            "fused_lm_head_sample");
+}
+
+// fused_lm_head_sample (tokens finalised) with the logprob epilogue: lp[m] = the sampled
+// token's logprob; lp_ws: fp32 scratch of 4 words per key (M * vocab / 16 records)
+void fused_lm_head_sample_lp(at::Tensor tokens, at::Tensor lp, at::Tensor keys, at::Tensor lp_ws,
+                             const at::Tensor& x, const at::Tensor& w, double eps,
+                             const at::Tensor& temperature, const at::Tensor& seeds,
+                             const at::Tensor& steps, int64_t waves, bool preshuffled) {
+  check_skinny(x, w, "fused_lm_head_sample_lp");
+  TORCH_CHECK(x.scalar_type() == w.scalar_type(), "fused_lm_head_sample_lp: 16-bit weights");
+  TORCH_CHECK(tokens.scalar_type() == at::kLong && keys.scalar_type() == at::kLong &&
+                  seeds.scalar_type() == at::kLong && steps.scalar_type() == at::kLong &&
+                  temperature.scalar_type() == at::kFloat && lp.scalar_type() == at::kFloat &&
+                  lp_ws.scalar_type() == at::kFloat,
+              "fused_lm_head_sample_lp: dtypes");
+  const int64_t M = x.size(0), slots = M * (w.size(0) / 16);
+  TORCH_CHECK(keys.numel() >= slots && tokens.numel() >= M && lp.numel() >= M &&
+                  temperature.numel() >= M && seeds.numel() >= M && steps.numel() >= M,
+              "fused_lm_head_sample_lp: keys needs M * (vocab / 16) entries");
+  TORCH_CHECK(lp_ws.numel() >= 4 * slots && lp_ws.is_contiguous() && lp.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(lp_ws.data_ptr()) % 16 == 0,
+              "fused_lm_head_sample_lp: lp_ws needs 4 * M * (vocab / 16) floats, 16-B aligned");
+  TORCH_CHECK(keys.device() == x.device() && lp_ws.device() == x.device() &&
+                  lp.device() == x.device() && tokens.device() == x.device(),
+              "fused_lm_head_sample_lp: one device");
+  const at::DeviceGuard g(x.device());
+  check_rc(atta_fused_lm_head_sample_lp(
+               tokens.data_ptr<int64_t>(), lp.data_ptr<float>(),
+               reinterpret_cast<unsigned long long*>(keys.data_ptr<int64_t>()), lp_ws.data_ptr(),
+               x.data_ptr(), w.data_ptr(), M, w.size(0), x.size(1), x.stride(0),
+               static_cast<float>(eps), temperature.data_ptr<float>(), seeds.data_ptr<int64_t>(),
+               steps.data_ptr<int64_t>(), waves, skinny_dtype(x, preshuffled), cur_stream()),
+           "fused_lm_head_sample_lp");
 }
 
 // Row-wise fp8 activation quantisation fused into norm / SiLU-mul / plain rows.
@@ -916,6 +979,10 @@ TORCH_LIBRARY(atta, m) {
       "fused_lm_head_sample(Tensor(a!) tokens, Tensor(b!) keys, Tensor x, Tensor w, float eps, "
       "Tensor temperature, Tensor seeds, Tensor steps, int finalize, int vocab_offset, "
       "int waves, bool preshuffled=False, Tensor? w_scale=None) -> ()");
+  m.def(
+      "fused_lm_head_sample_lp(Tensor(a!) tokens, Tensor(b!) lp, Tensor(c!) keys, "
+      "Tensor(d!) lp_ws, Tensor x, Tensor w, float eps, Tensor temperature, Tensor seeds, "
+      "Tensor steps, int waves, bool preshuffled=False) -> ()");
   m.def("sample_finalize(Tensor(a!) tokens, Tensor keys, int n_tiles) -> ()");
   m.def("skinny_gemm(Tensor(a!) y, Tensor x, Tensor w, Tensor? residual, int waves, "
         "bool preshuffled=False, Tensor? w_scale=None, int ksplit=1, "
@@ -960,6 +1027,8 @@ TORCH_LIBRARY(atta, m) {
   m.def("sample(Tensor(a!) out, Tensor logits, Tensor temperature, Tensor seeds, Tensor steps) -> ()");
   m.def("sample_topkp(Tensor(a!) out, Tensor logits, Tensor temperature, Tensor top_p, "
         "Tensor top_k, Tensor seeds, Tensor steps) -> ()");
+  m.def("token_logprobs(Tensor(a!) lp, Tensor(b!) top_ids, Tensor(c!) top_lp, Tensor logits, "
+        "Tensor tokens, int n_top) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(atta, CUDA, m) {
@@ -979,11 +1048,13 @@ TORCH_LIBRARY_IMPL(atta, CUDA, m) {
   m.impl("attention_decode", &attention_decode);
   m.impl("sample", &sample);
   m.impl("sample_topkp", &sample_topkp);
+  m.impl("token_logprobs", &token_logprobs);
   m.impl("skinny_gemm", &skinny_gemm);
   m.impl("prefill_gemm", &prefill_gemm);
   m.impl("fused_qkv_rope", &fused_qkv_rope);
   m.impl("fused_gate_up_silu", &fused_gate_up_silu);
   m.impl("fused_lm_head_sample", &fused_lm_head_sample);
+  m.impl("fused_lm_head_sample_lp", &fused_lm_head_sample_lp);
   m.impl("sample_finalize", &sample_finalize);
   m.impl("set_splitk_workspace", &set_splitk_workspace);
   m.impl("quant_rows_fp8", &quant_rows_fp8);

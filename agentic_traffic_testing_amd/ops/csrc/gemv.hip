@@ -92,8 +92,10 @@ static void launch_t(int dtype, dim3 grid, hipStream_t st, const SkinnyParams& p
   constexpr std::true_type yes{};
   constexpr std::false_type no{};
   auto by_layout = [&](auto t, auto nt_) {
-    if (w8) launch(t, nt_, yes, yes);
-    else if (ps) launch(t, nt_, yes, no);
+    if (w8) {
+      // (no fp8 build of the logprob sampler epilogue: route() sends none here)
+      if constexpr (EPI != EPI_SAMPLE_LP) launch(t, nt_, yes, yes);
+    } else if (ps) launch(t, nt_, yes, no);
     else launch(t, nt_, no, no);
   };
   auto by_nt = [&](auto t) {
@@ -184,6 +186,80 @@ __global__ void __launch_bounds__(kFinThreads) sample_finalize_kernel(
     }
   }
 }
+
+// (max, sum exp(l - max)) of two sets of logits -> of their union.  An empty set is
+// (-inf, 0): the guard keeps exp(-inf - -inf) out.
+__device__ __forceinline__ void lse_merge(float& m, float& s, float om, float os) {
+  const float nm = fmaxf(m, om);
+  if (nm > -__builtin_huge_valf()) s = s * __expf(m - nm) + os * __expf(om - nm);
+  m = nm;
+}
+
+// sample_finalize_kernel for the SAMPLE_LP epilogue: the same key reduction to the row's token
+// (same load shape: 1024 threads x 8 loads cover 8192 tiles per trip), and the row's logprob
+// from the per-tile records rec[m][tile] = {max_i, s_i, raw logit of the tile's winner}:
+//   logZ = gmax + log(sum_i s_i exp(max_i - gmax)),   lp[m] = l_win - logZ
+// with l_win read from the winning tile's record.  ids in the keys are global: vocab_offset is
+// the id of column 0.
+__global__ void __launch_bounds__(kFinThreads) sample_lp_finalize_kernel(
+    int64_t* out, float* lp, const unsigned long long* keys, const f32x4* rec, int n_tiles,
+    int vocab_offset) {
+  __shared__ unsigned long long red[kFinThreads / kWave];
+  __shared__ float rm[kFinThreads / kWave], rs[kFinThreads / kWave];
+  const int m = blockIdx.x;
+  const unsigned long long* row = keys + static_cast<int64_t>(m) * n_tiles;
+  const f32x4* rrow = rec + static_cast<int64_t>(m) * n_tiles;
+  unsigned long long best = 0ull;
+  float gm = -__builtin_huge_valf(), gs = 0.f;
+  for (int base = 0; base < n_tiles; base += 8 * kFinThreads) {
+    unsigned long long k[8];
+    f32x4 r[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int i = base + j * kFinThreads + threadIdx.x;
+      k[j] = i < n_tiles ? row[i] : 0ull;
+      r[j] = i < n_tiles ? rrow[i] : f32x4{-__builtin_huge_valf(), 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      best = k[j] > best ? k[j] : best;
+      lse_merge(gm, gs, r[j][0], r[j][1]);
+    }
+  }
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) {
+    const unsigned long long other = __shfl_xor(best, o, kWave);
+    best = other > best ? other : best;
+    const float om = __shfl_xor(gm, o, kWave), os = __shfl_xor(gs, o, kWave);
+    lse_merge(gm, gs, om, os);
+  }
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    red[threadIdx.x / kWave] = best;
+    rm[threadIdx.x / kWave] = gm;
+    rs[threadIdx.x / kWave] = gs;
+  }
+  __syncthreads();
+  if (threadIdx.x < kWave) {
+    const bool has = threadIdx.x < kFinThreads / kWave;
+    best = has ? red[threadIdx.x] : 0ull;
+    gm = has ? rm[threadIdx.x] : -__builtin_huge_valf();
+    gs = has ? rs[threadIdx.x] : 0.f;
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+      const unsigned long long other = __shfl_xor(best, o, kWave);
+      best = other > best ? other : best;
+      const float om = __shfl_xor(gm, o, kWave), os = __shfl_xor(gs, o, kWave);
+      lse_merge(gm, gs, om, os);
+    }
+    if (threadIdx.x == 0) {
+      const int id = static_cast<int>(0xFFFFFFFFu - static_cast<unsigned>(best & 0xFFFFFFFFull));
+      out[m] = id;
+      // the winner's tile; clamped so that keys no launch wrote can never index past the row
+      const int tile = min(max((id - vocab_offset) >> 4, 0), n_tiles - 1);
+      lp[m] = rrow[tile][2] - (gm + logf(gs));
+    }
+  }
+}
 }  // namespace atta
 
 using namespace atta;
@@ -242,14 +318,17 @@ void atta_get_wide_min_rows(int* m, int* m_silu) {
 //   MXFP4 (pre-shuffled)  any but SAMPLE    1 - 32             Skinny (its W4 build,
 //   MXFP4                 any but SAMPLE    > 32               None    gemv_w4.hip)
 //   MXFP4                 SAMPLE, the push  any                None
+// SAMPLE_LP (the sampler with the logprob record) routes as SAMPLE does, except that it has no
+// fp8 build at any row count: None.
 enum class Route { None, Skinny, Wide, MidM };
 static Route route(int M, bool ps, bool w8, bool w4, int epi) {
   if (M < 1) return Route::None;
-  if (w4) return M <= kSkinnyMaxM && epi != EPI_SAMPLE ? Route::Skinny : Route::None;
+  if (w4) return M <= kSkinnyMaxM && !epi_samples(epi) ? Route::Skinny : Route::None;
+  if (epi == EPI_SAMPLE_LP && w8) return Route::None;
   if (!ps) return M <= kSkinnyMaxM ? Route::Skinny : Route::None;
   const int wide_min = epi == EPI_SILU ? g_wide_min_m_silu : g_wide_min_m;
   if (M <= kSkinnyMaxM && (w8 || M < wide_min)) return Route::Skinny;
-  if (epi == EPI_SAMPLE && (w8 || M > kWideMaxM)) return Route::None;
+  if (epi_samples(epi) && (w8 || M > kWideMaxM)) return Route::None;
   if (M <= kWideMaxM) return Route::Wide;
   return M <= kMidmMaxM ? Route::MidM : Route::None;
 }
@@ -483,6 +562,31 @@ int atta_fused_lm_head_sample(int64_t* tokens, unsigned long long* keys, const v
     sample_finalize_kernel<false><<<M, kFinThreads, 0, stream>>>(tokens, keys, N / 16);
   else if (finalize == 2)
     sample_finalize_kernel<true><<<M, kFinThreads, 0, stream>>>(tokens, keys, N / 16);
+  return static_cast<int>(hipGetLastError());
+}
+
+// The same launch with the SAMPLE_LP epilogue and its finalize: tokens as above (bit-identical
+// keys) and lp[m] = the sampled token's logprob over the raw logits.  lp_ws: M * N / 16 records
+// of 16 B next to keys.  One GPU only (no key-only finalize): vocab_offset is 0.
+int atta_fused_lm_head_sample_lp(int64_t* tokens, float* lp, unsigned long long* keys,
+                                 void* lp_ws, const void* x, const void* w, int M, int N, int K,
+                                 int64_t x_stride, float eps, const float* temperature,
+                                 const int64_t* seeds, const int64_t* steps, int waves,
+                                 int dtype, hipStream_t stream) {
+  const int ps = (dtype & kPreshuffled) ? 1 : 0;
+  dtype &= ~kPreshuffled;
+  if (N % 16 != 0) return -1;
+  SkinnyParams p = base_params(x, w, M, N, K, x_stride, eps, ps, nullptr);
+  p.keys = keys;
+  p.key_stride = N / 16;
+  p.vocab_offset = 0;
+  p.temperature = temperature;
+  p.seeds = seeds;
+  p.steps = steps;
+  p.y = static_cast<uint16_t*>(lp_ws);  // lp_records()
+  if (const int rc = launch_routed<EPI_SAMPLE_LP>(p, N / 16, waves, 1, dtype, stream)) return rc;
+  sample_lp_finalize_kernel<<<M, kFinThreads, 0, stream>>>(tokens, lp, keys, lp_records(p), N / 16,
+                                                           0);
   return static_cast<int>(hipGetLastError());
 }
 

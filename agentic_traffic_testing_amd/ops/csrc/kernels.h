@@ -59,6 +59,12 @@ int atta_sample_topkp(int64_t* out, const void* logits, int rows, int vocab, int
                       const int* top_k, const int64_t* seeds, const int64_t* steps,
                       hipStream_t stream);
 
+// per-token logprobs of a materialised logits row: lp[r] = l[tokens[r]] - logsumexp(l), and the
+// n_top (0 .. 20) most likely ids with theirs, higher logit first, ties by lower id
+int atta_token_logprobs(float* lp, int* top_ids, float* top_lp, const void* logits,
+                        const int64_t* tokens, int rows, int vocab, int64_t stride,
+                        int logits_is_fp32, int n_top, hipStream_t stream);
+
 int atta_skinny_gemm_push(const void* x, const void* w, int M, int N, int K, int64_t x_stride,
                           int waves, int ksplit, const float* wscale, int dtype,
                           void* const* bases, int rank, int world, int64_t max_elems,
@@ -90,6 +96,14 @@ int atta_fused_lm_head_sample(int64_t* tokens, unsigned long long* keys, const v
                               const float* temperature, const int64_t* seeds,
                               const int64_t* steps, int finalize, int vocab_offset,
                               int waves, const float* wscale, int dtype, hipStream_t stream);
+
+// the same with the logprob epilogue (EPI_SAMPLE_LP): tokens finalised, lp[m] = logprob of
+// row m's token; lp_ws: M * N / 16 records of 16 B (16-B aligned), 16-bit weights, one GPU
+int atta_fused_lm_head_sample_lp(int64_t* tokens, float* lp, unsigned long long* keys,
+                                 void* lp_ws, const void* x, const void* w, int M, int N, int K,
+                                 int64_t x_stride, float eps, const float* temperature,
+                                 const int64_t* seeds, const int64_t* steps, int waves,
+                                 int dtype, hipStream_t stream);
 
 int atta_sample_finalize(int64_t* tokens, const unsigned long long* keys, int M, int n_tiles,
                          hipStream_t stream);

@@ -20,8 +20,15 @@ enum Epi {
   EPI_RESADD = 1,
   EPI_QKVROPE = 2,
   EPI_SILU = 3,
-  EPI_SAMPLE = 4
+  EPI_SAMPLE = 4,
+  // SAMPLE's keys, plus per (row, tile) the record the row's logprob is finished from
+  // (gemv.hip sample_lp_finalize_kernel): the tile's log-sum-exp partial over its 16 raw
+  // logits and the raw logit of its winning column
+  EPI_SAMPLE_LP = 5
 };
+
+// the LM-head sampler epilogues (unsplit, 16-bit weights only: route() in gemv.hip)
+constexpr bool epi_samples(int epi) { return epi == EPI_SAMPLE || epi == EPI_SAMPLE_LP; }
 
 template <typename T>
 struct MfmaK32;
@@ -70,7 +77,7 @@ __device__ __forceinline__ typename MfmaK32<T>::frag8 fp8x8_to_frag(uint32_t lo,
 struct SkinnyParams {
   const uint16_t* x;
   const uint16_t* w;
-  uint16_t* y;  // PLAIN / RESADD (in place) / SILU output / QKVROPE q output
+  uint16_t* y;  // PLAIN / RESADD (in place) / SILU output / QKVROPE q output / SAMPLE_LP records
   int64_t x_stride, y_stride;
   int M, N, K;
   float eps;  // > 0: fused RMSNorm (norm weight folded into W)
@@ -115,6 +122,13 @@ struct SkinnyParams {
   // scales, 64 B per 16-row tile and 128-wide K chunk (one dword per row, byte j = K step j)
   const uint8_t* bscale;
 };
+
+// SAMPLE_LP keeps its [M, key_stride] records {max, sum exp(l - max), winner's raw logit, 0}
+// (fp32, 16 B each) behind the otherwise unused output pointer y: the parameter block, and with
+// it every other kernel's argument layout, stays as it is.
+__device__ __host__ __forceinline__ f32x4* lp_records(const SkinnyParams& p) {
+  return reinterpret_cast<f32x4*>(p.y);
+}
 
 __device__ __forceinline__ unsigned ordered_bits(float f) {
   const unsigned u = __float_as_uint(f);
@@ -229,6 +243,45 @@ __device__ __forceinline__ void tile_epilogue(const SkinnyParams& p, const int t
       }
       // one plain store per (row, tile): no same-address atomics across the ~8k tiles
       if (n == 0 && m < p.M) p.keys[static_cast<int64_t>(m) * p.key_stride + tile] = key;
+    }
+  } else if constexpr (EPI == EPI_SAMPLE_LP) {
+    // SAMPLE's key (the same expression, so the same bits), and the tile's logprob record
+    // over the raw logits: before temperature and noise
+    for (int e = tid; e < 16 * 16 * MTMAX; e += nthr) {
+      const int m = e >> 4, n = e & 15;
+      unsigned long long key = 0ull;
+      float raw = -__builtin_huge_valf();
+      if (m < p.M) {
+        const float sc = norm ? inv_rms[m] : 1.f;
+        float v = to_f32<T>(from_f32<T>(red[m][n] * sc));  // bf16 logits, as F.linear
+        raw = v;
+        const float t = p.temperature[m];
+        const int idx = p.vocab_offset + tile * 16 + n;  // global id: TP == TP1 noise
+        if (t > 1e-5f)
+          v = v / t + gumbel_noise(static_cast<uint64_t>(p.seeds[m]),
+                                   static_cast<uint64_t>(p.steps[m]), static_cast<uint32_t>(idx));
+        key = (static_cast<unsigned long long>(ordered_bits(v)) << 32) |
+              static_cast<unsigned long long>(0xFFFFFFFFu - static_cast<unsigned>(idx));
+      }
+      float mx = raw;
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) {
+        const unsigned long long other = __shfl_xor(key, o, kWave);
+        key = other > key ? other : key;
+        mx = fmaxf(mx, __shfl_xor(mx, o, kWave));
+      }
+      float sum = m < p.M ? __expf(raw - mx) : 0.f;
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) sum += __shfl_xor(sum, o, kWave);
+      // the winning column of this row's 16 lanes (its id is in the key) hands over its logit
+      const int wn = static_cast<int>(0xFFFFFFFFu - static_cast<unsigned>(key) -
+                                      static_cast<unsigned>(p.vocab_offset + tile * 16));
+      const float lwin = __shfl(raw, wn & 15, 16);
+      if (n == 0 && m < p.M) {
+        const int64_t at = static_cast<int64_t>(m) * p.key_stride + tile;
+        p.keys[at] = key;
+        lp_records(p)[at] = f32x4{mx, sum, lwin, 0.f};
+      }
     }
   }
 }

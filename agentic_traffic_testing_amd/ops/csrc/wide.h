@@ -104,7 +104,7 @@ __device__ __forceinline__ void epi_load(const SkinnyParams& p, const int tile, 
         in.cs[j][3] = c4[17];
       }
     }
-  } else if constexpr (EPI == EPI_SAMPLE) {
+  } else if constexpr (epi_samples(EPI)) {
 #pragma unroll
     for (int j = 0; j < RPL; ++j) {
       const int m = in.ok[j] ? in.rows[j] : 0;
@@ -225,6 +225,37 @@ __device__ __forceinline__ void epi_apply(const SkinnyParams& p, const int tile,
         best = key > best ? key : best;
       }
       p.keys[static_cast<int64_t>(m) * p.key_stride + tile] = best;
+    }
+  } else if constexpr (EPI == EPI_SAMPLE_LP) {
+    // SAMPLE's key (the same expression, so the same bits) and the tile's logprob record over
+    // the raw logits (skinny.h, EPI_SAMPLE_LP)
+#pragma unroll
+    for (int j = 0; j < RPL; ++j) {
+      if (!in.ok[j]) continue;
+      const int m = in.rows[j];
+      const float sc = norm ? inv_rms[m - rbase] : 1.f;
+      unsigned long long best = 0ull;
+      float raw[16], mx = -__builtin_huge_valf(), lwin = 0.f;
+#pragma unroll
+      for (int n = 0; n < 16; ++n) {
+        float v = to_f32<T>(from_f32<T>(red[m - rbase][n] * sc));  // bf16 logits, as F.linear
+        raw[n] = v;
+        mx = fmaxf(mx, v);
+        const int idx = p.vocab_offset + tile * 16 + n;    // global id: TP == TP1 noise
+        if (in.temp[j] > 1e-5f)
+          v = v / in.temp[j] + gumbel_noise(in.seed[j], in.step[j], static_cast<uint32_t>(idx));
+        const unsigned long long key =
+            (static_cast<unsigned long long>(ordered_bits(v)) << 32) |
+            static_cast<unsigned long long>(0xFFFFFFFFu - static_cast<unsigned>(idx));
+        lwin = key > best ? raw[n] : lwin;
+        best = key > best ? key : best;
+      }
+      float sum = 0.f;
+#pragma unroll
+      for (int n = 0; n < 16; ++n) sum += __expf(raw[n] - mx);
+      const int64_t at = static_cast<int64_t>(m) * p.key_stride + tile;
+      p.keys[at] = best;
+      lp_records(p)[at] = f32x4{mx, sum, lwin, 0.f};
     }
   }
 }
@@ -649,6 +680,13 @@ inline int launch_epi(int epi, dim3 grid, hipStream_t st, const SkinnyParams& p,
         if constexpr (kNormOk) wide_kernel<T, WAVES, MT, EPI_SAMPLE, true, TPW><<<grid, blk, 0, st>>>(p, ntiles);
       } else {
         wide_kernel<T, WAVES, MT, EPI_SAMPLE, false, TPW><<<grid, blk, 0, st>>>(p, ntiles);
+      }
+      return 0;
+    case EPI_SAMPLE_LP:
+      if (norm) {
+        if constexpr (kNormOk) wide_kernel<T, WAVES, MT, EPI_SAMPLE_LP, true, TPW><<<grid, blk, 0, st>>>(p, ntiles);
+      } else {
+        wide_kernel<T, WAVES, MT, EPI_SAMPLE_LP, false, TPW><<<grid, blk, 0, st>>>(p, ntiles);
       }
       return 0;
     default: return -1;

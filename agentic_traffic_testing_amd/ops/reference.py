@@ -172,6 +172,31 @@ def sample_topkp(logits: torch.Tensor, temperature, top_p, top_k, seeds,
     return out.to(logits.device)
 
 
+def token_logprobs(logits: torch.Tensor, tokens: torch.Tensor, n_top: int = 0):
+    """Per-row logprobs of ``tokens`` and the ``n_top`` most likely ids with theirs, as
+    ops/csrc/logprobs.hip defines them: fp32 ``log_softmax`` over the raw logits (before
+    temperature, noise and top-k / top-p); higher logit first, equal logits by lower id.
+    Returns (lp [rows] fp32, top_ids [rows, n_top] int32, top_lp [rows, n_top] fp32)."""
+    ls = torch.log_softmax(logits.float(), dim=-1)
+    rows = ls.shape[0]
+    lp = ls.gather(1, tokens[:rows].long().view(-1, 1)).view(-1)
+    # a stable descending sort keeps equal values in index order
+    vals, order = torch.sort(ls, dim=-1, descending=True, stable=True)
+    return lp, order[:, :n_top].to(torch.int32), vals[:, :n_top].contiguous()
+
+
+def lm_head_sample_logprobs(x: torch.Tensor, w: torch.Tensor, eps: float, temperature, seeds,
+                            steps):
+    """What the fused LM head + sampler with the logprob epilogue computes: the tokens of
+    ``sample`` over the LM-head product rounded to the model dtype, and their logprobs
+    (``eps`` > 0: the final RMSNorm first, its weight folded into ``w``)."""
+    if eps > 0:
+        x = rms_norm(x, torch.ones(x.shape[1], dtype=x.dtype, device=x.device), eps)
+    logits = torch.nn.functional.linear(x, w)
+    toks = sample(logits, temperature, seeds, steps)
+    return toks, token_logprobs(logits, toks)[0]
+
+
 def _ordered_bits(v: float) -> int:
     import struct
 

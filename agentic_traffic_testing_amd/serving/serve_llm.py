@@ -3,8 +3,10 @@
 API-compatible with the reference's aiohttp front end over vLLM (llm/serve_llm.py):
 
 * ``POST /chat | /completion | /generate`` with ``{prompt|input, max_tokens?, request_id?,
-  system_prompt?, skip_chat_template?}`` -> ``{"output", "meta": {request_id, latency_ms,
-  queue_wait_s, prompt_tokens, completion_tokens, total_tokens, otel}}``; 400 on bad JSON /
+  system_prompt?, skip_chat_template?, logprobs?}`` -> ``{"output", "meta": {request_id,
+  latency_ms, queue_wait_s, prompt_tokens, completion_tokens, total_tokens, otel}}`` (with an
+  integer ``logprobs`` also ``"logprobs": {tokens, token_ids, token_logprobs,
+  top_logprobs}``, one entry per generated token); 400 on bad JSON /
   missing prompt, 503 before init, 500 ``Generation failed: ...`` (serve_llm.py:731-942);
 * ``GET /health | /ready | /live`` -> ``{"status": "ok"}``; ``GET /metrics`` -> Prometheus
   text of the exact ``llm_*`` families (serving/metrics.py);
@@ -210,6 +212,15 @@ async def handle_chat(request: web.Request) -> web.Response:
                 max_tokens = int(max_tokens)
             except (TypeError, ValueError):
                 max_tokens = None
+        # optional integer "logprobs" (SamplingParams.logprobs: 0 = the sampled tokens', N <= 20
+        # = also each position's N most likely tokens); absent: the response is unchanged
+        want_lp = data.get("logprobs")
+        if want_lp is not None:
+            try:
+                SamplingParams(logprobs=want_lp).check()
+            except ValueError as exc:
+                _leave()
+                return web.json_response({"error": str(exc)}, status=400)
         rid = request.headers.get("X-Request-ID") or data.get("request_id")
         request_id = str(rid) if rid else str(uuid.uuid4())[:8]
         span.set_attribute("app.request_id", request_id)
@@ -248,7 +259,7 @@ async def handle_chat(request: web.Request) -> web.Response:
 
         sp = SamplingParams(temperature=float(data.get("temperature", st.s.temperature)),
                             max_tokens=max(1, eff_new), ignore_eos=bool(data.get("ignore_eos", st.s.ignore_eos)),
-                            seed=data.get("seed"))
+                            seed=data.get("seed"), logprobs=want_lp)
         queue_wait = 0.0
         final = None
         try:
@@ -344,7 +355,26 @@ async def handle_chat(request: web.Request) -> web.Response:
             "finish_reason": final.finish_reason if final else None,
             "completion_tokens_text": st.tok.count(text),
         }
-        return web.json_response({"output": text, "meta": meta})
+        body = {"output": text, "meta": meta}
+        if want_lp is not None:
+            body["logprobs"] = _logprobs_body(st, final)
+        return web.json_response(body)
+
+
+def _logprobs_body(st: ServerState, final) -> dict:
+    """The "logprobs" object of a /chat response: four lists, one entry per generated token -
+    its text, id and logprob (raw logits: before temperature and top-k / top-p) and the
+    position's alternatives [{"token", "token_id", "logprob"}, ...], most likely first."""
+    ids = list(final.token_ids) if final is not None else []
+    lps = list(final.logprobs or []) if final is not None else []
+    tops = list(final.top_logprobs or []) if final is not None else []
+    return {
+        "tokens": [st.tok.decode([t]) for t in ids],
+        "token_ids": ids,
+        "token_logprobs": lps,
+        "top_logprobs": [[{"token": st.tok.decode([i]), "token_id": i, "logprob": v}
+                          for i, v in alts] for alts in tops],
+    }
 
 
 def _engine_spans(st: ServerState, wait_span, gen_span, final) -> None:

@@ -8,6 +8,9 @@ Same contract as reference tools/mcp_universe/openai_proxy.py:43-165:
   connection error is a 502 with ``error`` / ``status`` / ``backend_body`` (500 chars);
 * the reply is a ``chat.completion`` object with one ``stop`` choice; an empty backend
   output becomes ``"[Proxy] Local LLM backend returned empty output."``;
+* ``logprobs: true`` (with an optional ``top_logprobs: k``) is forwarded as the backend's
+  integer ``logprobs`` (``k`` or 0) and answered in ``choices[0].logprobs.content``; a request
+  without it is forwarded exactly as before (not in the reference, which ignores both);
 * ``GET /health`` and ``/ready`` report the backend URL; default port 8110.
 
 Deliberate fix (SURVEY §2.1 T5 notes the reference always returns null usage): when the
@@ -73,6 +76,30 @@ def _usage(data) -> dict:
     return {"prompt_tokens": None, "completion_tokens": None, "total_tokens": None}
 
 
+def _lp_entry(token, logprob) -> dict:
+    token = token if isinstance(token, str) else ""
+    return {"token": token, "logprob": logprob, "bytes": list(token.encode("utf-8"))}
+
+
+def _logprobs_content(data) -> list:
+    """OpenAI's ``choices[0].logprobs.content`` from the backend's "logprobs" object: one
+    {"token", "logprob", "bytes", "top_logprobs": [...]} per generated token (empty when the
+    backend sent none)."""
+    lp = data.get("logprobs") if isinstance(data, dict) else None
+    if not isinstance(lp, dict):
+        return []
+    toks, vals = lp.get("tokens") or [], lp.get("token_logprobs") or []
+    tops = lp.get("top_logprobs") or []
+    out = []
+    for i, (tok, val) in enumerate(zip(toks, vals)):
+        e = _lp_entry(tok, val)
+        alts = tops[i] if i < len(tops) and isinstance(tops[i], list) else []
+        e["top_logprobs"] = [_lp_entry(a.get("token"), a.get("logprob"))
+                             for a in alts if isinstance(a, dict)]
+        out.append(e)
+    return out
+
+
 async def handle_chat_completions(request: web.Request) -> web.Response:
     try:
         payload = await request.json()
@@ -90,6 +117,12 @@ async def handle_chat_completions(request: web.Request) -> web.Response:
             body["max_tokens"] = int(payload["max_tokens"])
     except (TypeError, ValueError):
         pass
+    # OpenAI's logprobs: true [+ top_logprobs: k] -> the backend's integer "logprobs" (0 = the
+    # sampled tokens' only); a request without them is forwarded as before
+    want_lp = payload.get("logprobs") is True
+    if want_lp:
+        k = payload.get("top_logprobs")
+        body["logprobs"] = k if isinstance(k, int) and not isinstance(k, bool) and k > 0 else 0
     url = request.app[BACKEND_KEY]
     try:
         async with request.app[SESSION_KEY].post(url, json=body) as resp:
@@ -102,15 +135,17 @@ async def handle_chat_completions(request: web.Request) -> web.Response:
     except Exception as exc:
         return web.json_response({"error": f"Error calling local LLM backend: {exc}"},
                                  status=502)
+    choice = {"index": 0,
+              "message": {"role": "assistant", "content": _output_text(data) or EMPTY_OUTPUT},
+              "finish_reason": "stop"}
+    if want_lp:
+        choice["logprobs"] = {"content": _logprobs_content(data)}
     return web.json_response({
         "id": f"chatcmpl-{uuid.uuid4().hex[:24]}",
         "object": "chat.completion",
         "created": int(time.time()),
         "model": payload.get("model", "local-llm"),
-        "choices": [{"index": 0,
-                     "message": {"role": "assistant",
-                                 "content": _output_text(data) or EMPTY_OUTPUT},
-                     "finish_reason": "stop"}],
+        "choices": [choice],
         "usage": _usage(data),
     })
 
