@@ -32,9 +32,36 @@ void check_dev(const at::Tensor& t, const char* name) {
   TORCH_CHECK(t.is_cuda(), "atta: ", name, " must be a GPU tensor");
 }
 
+// The row kernels (norm, SiLU-mul, RoPE) move 8 elements per access: 16-byte loads and stores
+// from the start of every row.  A base pointer or a row stride that breaks that alignment is
+// refused here, before anything is launched.
+void check_rows16(const at::Tensor& t, const char* op, const char* name) {
+  TORCH_CHECK(t.is_cuda(), "atta: ", op, ": ", name, " must be a GPU tensor");
+  TORCH_CHECK(t.element_size() == 2, op, ": ", name, " must be a 16-bit tensor");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(t.data_ptr()) % 16 == 0, op, ": ", name,
+              " must start 16-byte aligned");
+  TORCH_CHECK(t.dim() < 2 || t.size(0) <= 1 || t.stride(0) % 8 == 0, op, ": ", name,
+              " row stride must be a multiple of 8 elements, got ", t.dim() < 2 ? 0 : t.stride(0));
+}
+
+// out [rows, hidden] like x; w [hidden] contiguous, all of x's dtype and device.
+void check_norm_args(const at::Tensor& out, const at::Tensor& x, const at::Tensor& w,
+                     const char* op) {
+  TORCH_CHECK(out.dim() == 2 && out.sizes() == x.sizes() && out.scalar_type() == x.scalar_type() &&
+                  out.device() == x.device(),
+              op, ": out must match x in shape, dtype and device");
+  TORCH_CHECK(w.numel() == x.size(1) && w.is_contiguous() &&
+                  w.scalar_type() == x.scalar_type() && w.device() == x.device(),
+              op, ": weight [hidden] contiguous, of x's dtype and device");
+  check_rows16(x, op, "x");
+  check_rows16(out, op, "out");
+  check_rows16(w, op, "w");
+}
+
 void rms_norm(at::Tensor out, const at::Tensor& x, const at::Tensor& w, double eps) {
   check_dev(x, "x");
   TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && out.stride(1) == 1, "rms_norm: 2-D rows");
+  check_norm_args(out, x, w, "rms_norm");
   const at::DeviceGuard g(x.device());
   check_rc(atta_rms_norm(out.data_ptr(), nullptr, x.data_ptr(), w.data_ptr(), x.size(0),
                          x.size(1), x.stride(0), out.stride(0), 0, static_cast<float>(eps),
@@ -47,7 +74,11 @@ void fused_add_rms_norm(at::Tensor out, at::Tensor residual, const at::Tensor& x
   check_dev(x, "x");
   TORCH_CHECK(x.dim() == 2 && x.stride(1) == 1 && residual.stride(1) == 1 && out.stride(1) == 1,
               "fused_add_rms_norm: 2-D rows");
-  TORCH_CHECK(residual.sizes() == x.sizes(), "fused_add_rms_norm: residual shape");
+  TORCH_CHECK(residual.sizes() == x.sizes() && residual.scalar_type() == x.scalar_type() &&
+                  residual.device() == x.device(),
+              "fused_add_rms_norm: residual must match x in shape, dtype and device");
+  check_norm_args(out, x, w, "fused_add_rms_norm");
+  check_rows16(residual, "fused_add_rms_norm", "residual");
   const at::DeviceGuard g(x.device());
   check_rc(atta_rms_norm(out.data_ptr(), residual.data_ptr(), x.data_ptr(), w.data_ptr(),
                          x.size(0), x.size(1), x.stride(0), out.stride(0), residual.stride(0),
@@ -58,7 +89,15 @@ void fused_add_rms_norm(at::Tensor out, at::Tensor residual, const at::Tensor& x
 void silu_and_mul(at::Tensor out, const at::Tensor& x) {
   check_dev(x, "x");
   TORCH_CHECK(x.dim() == 2 && x.size(1) % 2 == 0 && x.stride(1) == 1, "silu_and_mul: x");
-  TORCH_CHECK(out.size(1) * 2 == x.size(1) && out.size(0) == x.size(0), "silu_and_mul: out");
+  TORCH_CHECK(out.dim() == 2 && out.size(1) * 2 == x.size(1) && out.size(0) == x.size(0) &&
+                  out.stride(1) == 1 && out.scalar_type() == x.scalar_type() &&
+                  out.device() == x.device(),
+              "silu_and_mul: out [rows, inter] of x's dtype and device");
+  check_rows16(x, "silu_and_mul", "x");
+  check_rows16(out, "silu_and_mul", "out");
+  // gate and up halves are both read 8 elements at a time
+  TORCH_CHECK(out.size(1) % 8 == 0, "silu_and_mul: inter must be a multiple of 8, got ",
+              out.size(1));
   const at::DeviceGuard g(x.device());
   check_rc(atta_silu_and_mul(out.data_ptr(), x.data_ptr(), x.size(0), out.size(1), x.stride(0),
                              out.stride(0), dtype_code(x), cur_stream()),
@@ -131,6 +170,35 @@ void rope_cache(at::Tensor q_out, at::Tensor k_cache, at::Tensor v_cache, const 
   TORCH_CHECK(k_cache.dim() == 4 && k_cache.size(1) == n_kv_heads && k_cache.size(3) == head_dim,
               "rope_cache: k_cache [nb, Hkv, BS, D]");
   TORCH_CHECK(v_cache.dim() == 4 && v_cache.size(2) == head_dim, "rope_cache: v_cache [nb,Hkv,D,BS]");
+  const int64_t T = qkv.size(0);
+  TORCH_CHECK(n_q_heads > 0 && n_kv_heads > 0 && head_dim > 0, "rope_cache: head counts > 0");
+  TORCH_CHECK(v_cache.size(0) == k_cache.size(0) && v_cache.size(1) == n_kv_heads &&
+                  v_cache.size(3) == k_cache.size(2) && k_cache.size(2) > 0,
+              "rope_cache: v_cache [nb, Hkv, D, BS] must match k_cache [nb, Hkv, BS, D]");
+  TORCH_CHECK(k_cache.is_contiguous() && v_cache.is_contiguous() &&
+                  k_cache.scalar_type() == qkv.scalar_type() &&
+                  v_cache.scalar_type() == qkv.scalar_type() &&
+                  k_cache.device() == qkv.device() && v_cache.device() == qkv.device(),
+              "rope_cache: caches contiguous, of qkv's dtype and device");
+  TORCH_CHECK(positions.is_contiguous() && slot_mapping.is_contiguous() &&
+                  positions.numel() >= T && slot_mapping.numel() >= T &&
+                  positions.device() == qkv.device() && slot_mapping.device() == qkv.device(),
+              "rope_cache: positions/slot_mapping contiguous [T] on qkv's device");
+  TORCH_CHECK(cos_sin.dim() == 2 && cos_sin.is_contiguous() && cos_sin.device() == qkv.device(),
+              "rope_cache: cos_sin contiguous on qkv's device");
+  TORCH_CHECK((q_out.dim() == 3 && q_out.size(1) == n_q_heads && q_out.size(2) == head_dim &&
+               q_out.stride(2) == 1 && q_out.stride(1) == head_dim) ||
+                  (q_out.dim() == 2 && q_out.size(1) == n_q_heads * head_dim &&
+                   q_out.stride(1) == 1),
+              "rope_cache: q_out [T, Hq, D] or [T, Hq * D] with dense rows");
+  TORCH_CHECK(q_out.size(0) == T && q_out.scalar_type() == qkv.scalar_type() &&
+                  q_out.device() == qkv.device(),
+              "rope_cache: q_out rows, dtype and device must match qkv");
+  // 16-byte accesses to the qkv rows, the q_out rows and the K-cache token rows
+  check_rows16(qkv, "rope_cache", "qkv");
+  check_rows16(q_out, "rope_cache", "q_out");
+  check_rows16(k_cache, "rope_cache", "k_cache");
+  TORCH_CHECK(head_dim % 16 == 0, "rope_cache: head_dim must be a multiple of 16, got ", head_dim);
   const int64_t q_out_stride = q_out.dim() == 3 ? q_out.stride(0) : q_out.stride(0);
   const at::DeviceGuard g(qkv.device());
   check_rc(atta_rope_cache(q_out.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),

@@ -477,3 +477,375 @@ def assert_exact(got, exp, dtype, atol: float = 0.0, what: str = "") -> float:
           f"rtol={rtol:.3e} atol={atol:.3e}")
     assert bad == 0, f"{what}: {bad} elements off the closed-form answer, max rel err {rel:.4g}"
     return rel
+
+
+# =========================================================================================
+# Row kernels (norm, SiLU-mul, RoPE + cache write, embed, fp8 row quantiser) against fp64
+# references that round exactly where the kernels do (tests/test_row_kernels_exact.py).
+# =========================================================================================
+ROW_DELTA = 2.0 ** -16  # relative distance to a rounding tie below which one step is allowed
+ROW_SHARE_CAP = {torch.bfloat16: 0.02, torch.float16: 0.08}
+ROW_SENTINEL = 0x5A5B   # int16 pattern every guarded buffer is filled with (0x5B as a byte)
+# format -> (explicit mantissa bits, exponent of the smallest normal, largest finite value)
+_ROW_FMT = {torch.bfloat16: (7, -126, float(torch.finfo(torch.bfloat16).max)),
+            torch.float16: (10, -14, 65504.0), "e4m3": (3, -6, 448.0)}
+_TWO = torch.tensor(2.0, dtype=torch.float64)
+
+
+def round_fmt(v, fmt, scale=None, delta: float = ROW_DELTA):
+    """Round fp64 ``v`` to the format once, ties to even, subnormals and overflow included.
+    Returns (rounded fp64, near): ``near`` marks the elements whose distance to a rounding tie
+    is at most delta * |v| (delta * ``scale`` where the error of the fp32 evaluation is
+    relative to the operands, not to a cancelling result)."""
+    p, emin, vmax = _ROW_FMT[fmt]
+    a = v.abs()
+    e = torch.frexp(a)[1]                                  # a = m * 2^e, m in [0.5, 1)
+    quantum = torch.pow(_TWO, (torch.clamp(e - 1, min=emin) - p).double())
+    t = a / quantum                                        # exact: a power-of-two divisor
+    r = torch.round(t) * quantum                           # torch.round: half to even
+    dist = (t - (torch.floor(t) + 0.5)).abs() * quantum
+    near = (dist <= delta * (a if scale is None else scale)) & (a > 0)
+    r = torch.where(r > vmax, torch.full_like(r, float("inf")), r)
+    return torch.copysign(r, v), near
+
+
+def row_ordered(t):
+    """Sign-magnitude bit patterns (16-bit floats, or uint8 e4m3 codes) as integers whose
+    difference counts representable steps."""
+    if t.dtype == torch.uint8:
+        b = t.int()
+        return torch.where((b & 0x80) != 0, -(b & 0x7F), b & 0x7F)
+    b = t.view(torch.int16).int() & 0xFFFF
+    return torch.where((b & 0x8000) != 0, -(b & 0x7FFF), b & 0x7FFF)
+
+
+def row_bits(t):
+    return t if t.dtype == torch.uint8 else t.view(torch.int16)
+
+
+def row_ok(got, ref, near=None, steps: int = 0):
+    """Per element: bit-equal to ``ref``, or - only where ``near`` - within ``steps``
+    representable steps of it.  Returns (mask, step distances)."""
+    got, ref = got.cpu(), ref.cpu()
+    assert got.shape == ref.shape and got.dtype == ref.dtype, (got.shape, ref.shape)
+    ok = row_bits(got) == row_bits(ref)
+    dist = (row_ordered(got) - row_ordered(ref)).abs()
+    if near is not None and steps:
+        ok = ok | (near & (dist <= steps))
+    return ok, dist
+
+
+def row_mismatches(got, ref, near=None, steps: int = 0):
+    """Elements that break the rule of ``row_ok``: (count, largest step distance)."""
+    ok, dist = row_ok(got, ref, near, steps)
+    worst = int(dist[~ok].max()) if bool((~ok).any()) else 0
+    return int((~ok).sum()), worst
+
+
+def assert_rows(got, ref, near=None, steps: int = 0, what: str = ""):
+    bad, worst = row_mismatches(got, ref, near, steps)
+    share = float(near.float().mean()) if near is not None and near.numel() else 0.0
+    print(f"ROWS {what} n={ref.numel()} boundary_share={share:.4%} bad={bad} worst_steps={worst}")
+    assert bad == 0, f"{what}: {bad} of {ref.numel()} elements off the fp64 reference " \
+                     f"(worst {worst} steps)"
+    return share
+
+
+def rms_norm_ref64(x, w, eps: float, res=None, mutant: str | None = None):
+    """(out, near, residual): out = round(round(x * rsqrt(mean(x^2) + eps)) * w) in x's dtype
+    with x <- round(x + res) first when ``res`` is given.  ``near`` marks the elements whose
+    first rounding is within ROW_DELTA of a tie; the second rounds an exact product of two
+    T values, which fp32 holds exactly, so it can never differ.  Such elements may move by 2
+    steps: one step of the normalised value is up to 2 steps of the product."""
+    dt = x.dtype
+    xd = x.double()
+    r = None
+    if res is not None:
+        exact = xd + res.double()
+        r = round_fmt(exact, dt)[0]
+        xd = exact if mutant == "norm_of_unrounded_sum" else r
+    h = x.shape[1]
+    sq = xd * xd
+    if mutant == "ss_drop_last":
+        sq = sq[:, :-8]
+    elif mutant == "ss_drop_mid":
+        m = (h // 16) * 8
+        sq = torch.cat([sq[:, :m], sq[:, m + 8:]], dim=1)
+    ss = sq.sum(-1, keepdim=True)
+    div = -(-h // 2048) * 2048 if mutant == "mean_pad2048" else h
+    inv = 1.0 / torch.sqrt(ss / div + float(np.float32(eps)))
+    if mutant == "no_round":
+        out = round_fmt(xd * inv * w.double(), dt)[0]
+        return out.to(dt), torch.zeros_like(out, dtype=torch.bool), r
+    n, near = round_fmt(xd * inv, dt)
+    out = round_fmt(n * w.double(), dt)[0]
+    return out.to(dt), near, (None if r is None else r.to(dt))
+
+
+SILU_EXACT_GATE = 16.0  # |gate| up to here: the boundary rule; beyond: 2 steps everywhere
+
+
+def silu_ref64(x, mutant: str | None = None):
+    """(out, near, product): out = round(round(silu(gate)) * up); ``product`` is the fp64
+    value before the last rounding (what the fp8 SiLU mode quantises)."""
+    dt = x.dtype
+    i = x.shape[1] // 2
+    g, u = x[:, :i].double(), x[:, i:].double()
+    s64 = g / (1.0 + torch.exp(-g))
+    if mutant == "no_round":
+        out = round_fmt(s64 * u, dt)[0]
+        return out.to(dt), torch.zeros_like(out, dtype=torch.bool), s64 * u
+    s, near = round_fmt(s64, dt)
+    prod = s * u
+    return round_fmt(prod, dt)[0].to(dt), near | (g.abs() > SILU_EXACT_GATE), prod
+
+
+def embed_ref(table, ids, prev=None, flag: int = 0, mutant: str | None = None):
+    tok = prev[: ids.shape[0]].long() if (prev is not None and flag) else ids.long()
+    v = table.shape[0]
+    tok = tok % v if mutant == "no_clamp" else tok.clamp(0, v - 1)
+    return table[tok]
+
+
+def rope_ref64(qkv, pos, slots, cos_sin, k_cache, v_cache, hq, hkv, d, mutant: str | None = None):
+    """fp64 RoPE + paged-cache write over copies of the given caches.  Returns (q [T, hq, d],
+    q_near, k_cache, k_near, v_cache); one rounding of x1 * c -+ x2 * s evaluated in fp64, the
+    boundary window relative to |x1 c| + |x2 s| (the fp32 error of a cancelling sum is
+    relative to its terms)."""
+    dt = qkv.dtype
+    t = qkv.shape[0]
+    half = d // 2
+    p = pos.long()
+    if mutant == "pos_plus1":
+        p = (p + 1).clamp(max=cos_sin.shape[0] - 1)
+    cs = cos_sin[p].double()
+    c, s = cs[:, None, :half], cs[:, None, half:]
+    if mutant == "pair_shift":  # the 16 lowest-frequency pairs read their neighbour's entry
+        idx = torch.arange(half)
+        idx[half - 16:] = (idx[half - 16:] + 1).clamp(max=half - 1)
+        idx[half - 1] = half - 2
+        c, s = c[..., idx], s[..., idx]
+
+    def rot(xh):
+        x1, x2 = xh[..., :half].double(), xh[..., half:].double()
+        mag = (x1 * c).abs() + (x2 * s).abs()
+        mag2 = (x2 * c).abs() + (x1 * s).abs()
+        o1, n1 = round_fmt(x1 * c - x2 * s, dt, scale=mag)
+        o2, n2 = round_fmt(x2 * c + x1 * s, dt, scale=mag2)
+        return torch.cat([o1, o2], -1).to(dt), torch.cat([n1, n2], -1)
+
+    q, qn = rot(qkv[:, : hq * d].reshape(t, hq, d))
+    k, kn = rot(qkv[:, hq * d:(hq + hkv) * d].reshape(t, hkv, d))
+    v = qkv[:, (hq + hkv) * d:(hq + 2 * hkv) * d].reshape(t, hkv, d)
+    kc, vc = k_cache.clone(), v_cache.clone()
+    knear = torch.zeros(kc.shape, dtype=torch.bool)
+    nb, _, bs, _ = kc.shape
+    sl = slots.long()
+    live = sl >= 0
+    sk = (sl[live] + 1) % (nb * bs) if mutant == "k_slot_plus1" else sl[live]
+    kc[sk // bs, :, sk % bs, :] = k[live]
+    knear[sk // bs, :, sk % bs, :] = kn[live]
+    sv = sl[live]
+    if mutant == "v_swapped":  # dim and in-page offset exchanged: the K layout used for V
+        vc.view(nb, hkv, bs, d)[sv // bs, :, sv % bs, :] = v[live]
+    else:
+        vc[sv // bs, :, :, sv % bs] = v[live]
+    return q, qn, kc, knear, vc
+
+
+QUANT_EXACT_SCALE_MODES = (1, 2)  # SiLU and plain: the row amax is an exact fp32 value
+
+
+def quant_values64(x, mode: int, w=None, eps: float = 1e-5, res=None):
+    """(values fp64 [M, width], residual) - what quant_rows_fp8 quantises in each mode: the
+    norm modes without the two roundings to T of rms_norm (the kernel keeps fp32), the SiLU
+    mode with silu rounded to T and the product exact."""
+    dt = x.dtype
+    if mode == 2:
+        return x.double(), None
+    if mode == 1:
+        return silu_ref64(x)[2], None
+    r = None
+    xd = x.double()
+    if mode == 3:
+        r = round_fmt(xd + res.double(), dt)[0]
+        xd = r
+    inv = 1.0 / torch.sqrt((xd * xd).mean(-1, keepdim=True) + float(np.float32(eps)))
+    return xd * w.double() * inv, (None if r is None else r.to(dt))
+
+
+def fp8_codes64(vq, mutant: str | None = None):
+    """Round-to-nearest-even e4m3fn codes of fp64 values (saturating at +-448) and the mask
+    of values within ROW_DELTA of a code midpoint."""
+    vq = vq.clamp(-448.0, 448.0)
+    r, near = round_fmt(vq, "e4m3")
+    if mutant == "rtz":
+        up = r.abs() > vq.abs()
+        a = vq.abs()
+        quantum = torch.pow(_TWO, (torch.clamp(torch.frexp(a)[1] - 1, min=-6) - 3).double())
+        r = torch.where(up, torch.copysign(r.abs() - quantum, vq), r)
+    elif mutant == "flush_subnormal":
+        r = torch.where(r.abs() < 2.0 ** -6, torch.copysign(torch.zeros_like(r), vq), r)
+    return r.float().to(torch.float8_e4m3fn).view(torch.uint8), near
+
+
+def quant_model(v64, mutant: str | None = None):
+    """The definition applied to exact row values: s = fp32(amax) / 448 (1 for a zero row),
+    codes = e4m3 round-to-nearest-even of v / s.  The wrong variants the tests must catch."""
+    src = v64[:, :-8] if mutant == "scale_drop_last" else v64
+    amax = src.abs().amax(-1).float()
+    s = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax))
+    return fp8_codes64(v64 / s.double()[:, None], mutant)[0], s
+
+
+def quant_violations(codes, scale, v64, exact_scale: bool, code_steps: int = 0, alts=()):
+    """How a (codes, scale) result breaks the rules, as a list of strings (empty: it holds).
+    Scale: one fp32 step around fp32(amax) / 448 where the amax is exact (plain and SiLU),
+    relative ROW_DELTA around the fp64 value otherwise.  Codes: the round-to-nearest-even
+    code of value / (the scale returned); the adjacent code only within ROW_DELTA of a code
+    midpoint (``code_steps`` = 1: adjacent everywhere, the rule of the CPU norm path).
+    ``alts``: further admissible value tensors (SiLU mode: silu_neighbours64); a code passes
+    if it passes for any of them."""
+    codes, scale = codes.cpu(), scale.cpu().reshape(-1).float()
+    out = []
+    amax = v64.abs().amax(-1)
+    want = torch.where(amax > 0, amax.float() / 448.0, torch.ones_like(amax).float())
+    if exact_scale:
+        lo = torch.nextafter(want, torch.zeros_like(want))
+        hi = torch.nextafter(want, torch.full_like(want, float("inf")))
+        ok = (scale == want) | (scale == lo) | (scale == hi)
+    else:
+        w64 = torch.where(amax > 0, amax / 448.0, torch.ones_like(amax))
+        ok = ((scale.double() - w64).abs() <= ROW_DELTA * w64)
+    if not bool(ok.all()):
+        i = int((~ok).nonzero()[0])
+        out.append(f"scale of row {i}: {float(scale[i])!r}, expected {float(want[i])!r}")
+    if not bool((scale > 0).all()):
+        return out + ["a scale is not positive"]
+    ok = dist = None
+    for v in (v64, *alts):
+        ref, near = fp8_codes64(v / scale.double()[:, None])
+        k, d = row_ok(codes, ref, torch.ones_like(near) if code_steps else near, 1)
+        ok, dist = (k, d) if ok is None else (ok | k, torch.minimum(dist, d))
+    if not bool(ok.all()):
+        r, c = (int(i) for i in (~ok).nonzero()[0])
+        out.append(f"{int((~ok).sum())} of {ok.numel()} codes off (worst {int(dist[~ok].max())} "
+                   f"steps), first at [{r}, {c}]: code {int(codes[r, c]):#x}, value / scale "
+                   f"{float(v64[r, c] / scale[r].double())!r}")
+    return out
+
+
+def silu_neighbours64(x):
+    """The fp8 SiLU mode's values with silu one step of T above / below the reference's,
+    on the elements whose silu rounding is a boundary one (unchanged elsewhere): what the
+    kernel may hold there under the boundary rule of silu_and_mul."""
+    dt = x.dtype
+    i = x.shape[1] // 2
+    g, u = x[:, :i].double(), x[:, i:].double()
+    s, near = round_fmt(g / (1.0 + torch.exp(-g)), dt)
+    bits = s.to(dt).view(torch.int16)
+    near = near & ((bits & 0x7FFF) != 0)
+    return [torch.where(near, (bits + d).view(dt).double(), s) * u for d in (1, -1)]
+
+
+E4M3_FINITE_CODES = [c for c in range(256) if (c & 0x7F) != 0x7F]
+
+
+def e4m3_values():
+    """Every finite e4m3fn value, both signs and both zeros: (codes uint8, values fp32)."""
+    codes = torch.tensor(E4M3_FINITE_CODES, dtype=torch.uint8)
+    return codes, codes.view(torch.float8_e4m3fn).float()
+
+
+def e4m3_midpoints():
+    """The exact midpoints between adjacent e4m3fn magnitudes (subnormal range included,
+    the one between 0 and the smallest subnormal too), both signs, as fp32."""
+    mag = torch.arange(0, 0x7F, dtype=torch.uint8).view(torch.float8_e4m3fn).float()
+    mid = (mag[:-1] + mag[1:]) / 2
+    return torch.cat([mid, -mid])
+
+
+@functools.lru_cache(maxsize=None)
+def _needle_tables():
+    # integers with at most 8 significant bits (exact in bf16), and the sums of two squares
+    allowed = [n for n in range(1, 1024) if (n >> max(0, n.bit_length() - 8)) << max(
+        0, n.bit_length() - 8) == n]
+    pairs = {}
+    for i, a in enumerate(allowed):
+        for b in allowed[i:]:
+            pairs.setdefault(a * a + b * b, (a, b))
+    return allowed, pairs
+
+
+@functools.lru_cache(maxsize=None)
+def needle_vector(hidden: int):
+    """Eight integers of at most 8 significant bits whose squares sum to 63 * hidden + 8:
+    with hidden - 8 elements of magnitude 1 beside them the row's mean square is exactly 64,
+    its rms 8, and 63/64 of its energy sits in the eight."""
+    allowed, pairs = _needle_tables()
+    target = 63 * hidden + 8
+    base = max(a for a in allowed if 8 * a * a <= target)
+    rest = target - 4 * base * base
+    near = sorted(allowed, key=lambda a: abs(a * a - rest // 4))
+    for p in near[:64]:
+        for q in near[:64]:
+            got = pairs.get(rest - p * p - q * q)
+            if got:
+                vec = (base, p, base, got[0], base, q, base, got[1])
+                assert sum(n * n for n in vec) == target
+                return vec
+    raise AssertionError(f"no needle vector for hidden {hidden}")
+
+
+def needle_positions(hidden: int):
+    """Vector indices the needle visits: every vector up to hidden 4096; above, both sides of
+    every 64-vector boundary (the first and last lane of every iteration of each norm kernel
+    and every wave boundary inside a 256-thread iteration), vector 0 and the last vector."""
+    nvec = hidden // 8
+    if hidden <= 4096:
+        return list(range(nvec))
+    pos = {0, nvec - 1}
+    for b in range(64, nvec, 64):
+        pos.update((b - 1, b))
+    return sorted(pos)
+
+
+def needle_rows(hidden: int, rows: int, dtype):
+    """(x [rows, hidden], w [hidden], expected out) with row r's needle at vector
+    needle_positions(hidden)[r % len]: x * (1 / 8) * w exactly, every value representable, so
+    the comparison allows nothing."""
+    vec = torch.tensor(needle_vector(hidden), dtype=torch.float64)
+    pos = needle_positions(hidden)
+    col = torch.arange(hidden)
+    r = torch.arange(rows)
+    x = torch.where(((col[None, :] * 7 + r[:, None] * 3) % 5) < 2, -1.0, 1.0).double()
+    for i in range(rows):
+        p = pos[i % len(pos)] * 8
+        x[i, p:p + 8] = torch.roll(vec, i % 8) * (-1.0 if i % 3 == 1 else 1.0)
+    w = torch.pow(_TWO, ((col % 5) - 2).double()) * torch.where(col % 3 == 0, -1.0, 1.0)
+    out = x / 8.0 * w
+    xt, wt, ot = x.to(dtype), w.to(dtype), out.to(dtype)
+    assert bool((xt.double() == x).all()) and bool((ot.double() == out).all())
+    return xt, wt, ot
+
+
+ROPE_EXACT_ALPHABET = (0.0, 1.0, -1.0, 2.0, -2.0, 4.0, -4.0, 0.5, -0.5)
+
+
+def rope_exact_table(max_pos: int, d: int):
+    """A synthetic cos|sin table of 0, +-1 and +- powers of two; the (cos, sin) pair differs
+    between neighbouring positions and neighbouring dims.  With qkv values that are small even
+    integers every rotated value is an integer below 256: exact in bf16 and fp16."""
+    half = d // 2
+    p = torch.arange(max_pos)[:, None]
+    i = torch.arange(half)[None, :]
+    code = (p * 37 + i * 11 + 1) % 81
+    alpha = torch.tensor(ROPE_EXACT_ALPHABET, dtype=torch.float32)
+    return torch.cat([alpha[code // 9], alpha[code % 9]], dim=1).contiguous()
+
+
+def rope_exact_qkv(t: int, width: int, dtype):
+    """Even integers in [-14, 14] coding (token, column)."""
+    tok = torch.arange(t)[:, None]
+    col = torch.arange(width)[None, :]
+    return ((((tok * 5 + col * 7 + (col // 8) * 3) % 15) - 7) * 2).to(dtype)
