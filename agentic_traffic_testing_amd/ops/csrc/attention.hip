@@ -21,6 +21,7 @@
 //       set (the G heads of one token) and split the partition's KV tiles round-robin; the
 //       4 partial (m, l, O) are merged through LDS.  With >1 partition the merged result is
 //       written as fp32 (O, lse) and `attn_combine_kernel` reduces partitions.
+#include "attention_decode_core.h"  // Mfma<T>, the MFMA pair of these kernels
 #include "common.h"
 #include "kernels.h"
 
@@ -28,30 +29,6 @@ namespace atta {
 
 constexpr int kD = 128;
 constexpr float kNegInf = -__builtin_huge_valf();
-
-template <typename T>
-struct Mfma;
-template <>
-struct Mfma<__bf16> {
-  typedef bf16x8 frag8;
-  __device__ static __forceinline__ f32x4 qk(frag8 a, frag8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, c, 0, 0, 0);
-  }
-  __device__ static __forceinline__ f32x4 pv(i16x4 a, i16x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16bf16_1k(a, b, c, 0, 0, 0);
-  }
-};
-template <>
-struct Mfma<_Float16> {
-  typedef f16x8 frag8;
-  __device__ static __forceinline__ f32x4 qk(frag8 a, frag8 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0);
-  }
-  __device__ static __forceinline__ f32x4 pv(i16x4 a, i16x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x16f16(__builtin_bit_cast(f16x4, a),
-                                                 __builtin_bit_cast(f16x4, b), c, 0, 0, 0);
-  }
-};
 
 struct AttnParams {
   uint16_t* out;            // [n_q_tokens, Hq, D]

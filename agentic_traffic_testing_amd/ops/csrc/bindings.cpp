@@ -716,31 +716,46 @@ void sample_finalize(at::Tensor tokens, const at::Tensor& keys, int64_t n_tiles)
            "sample_finalize");
 }
 
+// attention_decode_v2 and attention_decode_mq: the same arguments, checks and call, into
+// `entry` (the two entry points share a signature).
+static void decode_attention_op(decltype(&atta_attention_decode_v2) entry, const char* name,
+                                at::Tensor out, at::Tensor part_out, at::Tensor part_lse,
+                                at::Tensor counters, const at::Tensor& q,
+                                const at::Tensor& k_cache, const at::Tensor& v_cache,
+                                const at::Tensor& block_tables, const at::Tensor& seq_kvlen,
+                                const at::Tensor& seq_qstart, int64_t num_seqs,
+                                int64_t max_parts, int64_t part_tokens, int64_t n_q_heads,
+                                int64_t n_kv_heads, double scale) {
+  check_dev(q, "q");
+  TORCH_CHECK(block_tables.scalar_type() == at::kInt && seq_kvlen.scalar_type() == at::kInt &&
+                  seq_qstart.scalar_type() == at::kInt && counters.scalar_type() == at::kInt,
+              name, ": int32 metadata");
+  if (num_seqs < 0) num_seqs = seq_kvlen.size(0);
+  TORCH_CHECK(num_seqs <= seq_kvlen.size(0), name, ": num_seqs");
+  TORCH_CHECK(part_out.numel() >= num_seqs * n_kv_heads * max_parts * 16 * 128 &&
+                  part_lse.numel() >= num_seqs * n_kv_heads * max_parts * 16 &&
+                  counters.numel() >= num_seqs * n_kv_heads,
+              name, ": workspace too small");
+  const at::DeviceGuard g(q.device());
+  check_rc(entry(out.data_ptr(), part_out.data_ptr<float>(), part_lse.data_ptr<float>(),
+                 counters.data_ptr<int>(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
+                 block_tables.data_ptr<int>(), seq_kvlen.data_ptr<int>(),
+                 seq_qstart.data_ptr<int>(), num_seqs, max_parts, part_tokens, n_q_heads,
+                 n_kv_heads, k_cache.size(3), k_cache.size(2), block_tables.stride(0),
+                 q.stride(0), out.stride(0), static_cast<float>(scale), dtype_code(q),
+                 cur_stream()),
+           name);
+}
+
 void attention_decode_v2(at::Tensor out, at::Tensor part_out, at::Tensor part_lse,
                          at::Tensor counters, const at::Tensor& q, const at::Tensor& k_cache,
                          const at::Tensor& v_cache, const at::Tensor& block_tables,
                          const at::Tensor& seq_kvlen, const at::Tensor& seq_qstart,
                          int64_t num_seqs, int64_t max_parts, int64_t part_tokens,
                          int64_t n_q_heads, int64_t n_kv_heads, double scale) {
-  check_dev(q, "q");
-  TORCH_CHECK(block_tables.scalar_type() == at::kInt && seq_kvlen.scalar_type() == at::kInt &&
-                  seq_qstart.scalar_type() == at::kInt && counters.scalar_type() == at::kInt,
-              "attention_decode_v2: int32 metadata");
-  if (num_seqs < 0) num_seqs = seq_kvlen.size(0);
-  TORCH_CHECK(num_seqs <= seq_kvlen.size(0), "attention_decode_v2: num_seqs");
-  TORCH_CHECK(part_out.numel() >= num_seqs * n_kv_heads * max_parts * 16 * 128 &&
-                  part_lse.numel() >= num_seqs * n_kv_heads * max_parts * 16 &&
-                  counters.numel() >= num_seqs * n_kv_heads,
-              "attention_decode_v2: workspace too small");
-  const at::DeviceGuard g(q.device());
-  check_rc(atta_attention_decode_v2(
-               out.data_ptr(), part_out.data_ptr<float>(), part_lse.data_ptr<float>(),
-               counters.data_ptr<int>(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-               block_tables.data_ptr<int>(), seq_kvlen.data_ptr<int>(), seq_qstart.data_ptr<int>(),
-               num_seqs, max_parts, part_tokens, n_q_heads, n_kv_heads, k_cache.size(3),
-               k_cache.size(2), block_tables.stride(0), q.stride(0), out.stride(0),
-               static_cast<float>(scale), dtype_code(q), cur_stream()),
-           "attention_decode_v2");
+  decode_attention_op(atta_attention_decode_v2, "attention_decode_v2", out, part_out, part_lse,
+                      counters, q, k_cache, v_cache, block_tables, seq_kvlen, seq_qstart,
+                      num_seqs, max_parts, part_tokens, n_q_heads, n_kv_heads, scale);
 }
 
 void attention_decode_mq(at::Tensor out, at::Tensor part_out, at::Tensor part_lse,
@@ -749,28 +764,13 @@ void attention_decode_mq(at::Tensor out, at::Tensor part_out, at::Tensor part_ls
                          const at::Tensor& seq_kvlen, const at::Tensor& seq_qstart,
                          int64_t num_seqs, int64_t max_parts, int64_t part_tokens,
                          int64_t n_q_heads, int64_t n_kv_heads, double scale) {
-  check_dev(q, "q");
-  TORCH_CHECK(block_tables.scalar_type() == at::kInt && seq_kvlen.scalar_type() == at::kInt &&
-                  seq_qstart.scalar_type() == at::kInt && counters.scalar_type() == at::kInt,
-              "attention_decode_mq: int32 metadata");
-  if (num_seqs < 0) num_seqs = seq_kvlen.size(0);
-  TORCH_CHECK(num_seqs <= seq_kvlen.size(0) && num_seqs < seq_qstart.size(0),
+  TORCH_CHECK((num_seqs < 0 ? seq_kvlen.size(0) : num_seqs) < seq_qstart.size(0),
               "attention_decode_mq: num_seqs");
   TORCH_CHECK(part_tokens == 64 || part_tokens == 128 || part_tokens == 256,
               "attention_decode_mq: partitions of 64, 128 or 256 tokens");
-  TORCH_CHECK(part_out.numel() >= num_seqs * n_kv_heads * max_parts * 16 * 128 &&
-                  part_lse.numel() >= num_seqs * n_kv_heads * max_parts * 16 &&
-                  counters.numel() >= num_seqs * n_kv_heads,
-              "attention_decode_mq: workspace too small");
-  const at::DeviceGuard g(q.device());
-  check_rc(atta_attention_decode_mq(
-               out.data_ptr(), part_out.data_ptr<float>(), part_lse.data_ptr<float>(),
-               counters.data_ptr<int>(), q.data_ptr(), k_cache.data_ptr(), v_cache.data_ptr(),
-               block_tables.data_ptr<int>(), seq_kvlen.data_ptr<int>(), seq_qstart.data_ptr<int>(),
-               num_seqs, max_parts, part_tokens, n_q_heads, n_kv_heads, k_cache.size(3),
-               k_cache.size(2), block_tables.stride(0), q.stride(0), out.stride(0),
-               static_cast<float>(scale), dtype_code(q), cur_stream()),
-           "attention_decode_mq");
+  decode_attention_op(atta_attention_decode_mq, "attention_decode_mq", out, part_out, part_lse,
+                      counters, q, k_cache, v_cache, block_tables, seq_kvlen, seq_qstart,
+                      num_seqs, max_parts, part_tokens, n_q_heads, n_kv_heads, scale);
 }
 
 void set_gemv_trace(const c10::optional<at::Tensor>& trace) {

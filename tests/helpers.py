@@ -199,7 +199,8 @@ def census_max_keys(dtype) -> int:
 
 
 def decode_waves(part_tokens: int) -> int:
-    """Waves per workgroup of attention_decode_v2's instantiation for this partition size."""
+    """Waves per workgroup of attention_decode_v2's instantiation for this partition size
+    (attention_decode_core.h ``launch``; the 128-token switch is attention_decode.hip's)."""
     w128 = 8
     try:
         if int(os.environ.get("ATTA_ATTN128_WAVES", "8")) == 4:
@@ -210,7 +211,7 @@ def decode_waves(part_tokens: int) -> int:
 
 
 def decode_merge_trip(part_tokens: int, g: int) -> int:
-    """Partitions one trip of the last arriver's merge loop folds (attention_decode.hip: NG
+    """Partitions one trip of the last arriver's merge loop folds (attention_decode_core.h: ng
     merge groups of G * 16 threads, PPI partitions each)."""
     ng = min(decode_waves(part_tokens) * 64 // (g * 16), 16)
     return ng * (8 if ng <= 4 else 4)
