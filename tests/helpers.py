@@ -850,3 +850,218 @@ def rope_exact_qkv(t: int, width: int, dtype):
     tok = torch.arange(t)[:, None]
     col = torch.arange(width)[None, :]
     return ((((tok * 5 + col * 7 + (col // 8) * 3) % 15) - 7) * 2).to(dtype)
+
+
+# =========================================================================================
+# Wide / mid-M / prefill GEMMs on exact integer operands (tests/test_gemm_exact.py).
+#
+# x holds +-1 (norm-folded epilogues: row m holds +-2^(m % 3)), w holds +-1 with +-2 on one
+# entry in eight up to K = 1536 and pure +-1 beyond, so every product and every partial sum
+# is an integer far below 2^24: fp32 accumulation is exact in any order, for any split-K plan
+# and any K-group combine.  The expectation is the exact product (fp64 holds it) rounded once
+# where wide::epi_apply rounds, compared by bit equality with the row-kernel comparator above.
+# Cases are built for the largest row count a test uses; row counts below it are slices.
+# =========================================================================================
+from dataclasses import replace  # noqa: E402  (this section's only new import)
+
+GEMM_EPS = 1e-5
+GEMM_TWO_MAG_MAX_K = 1536     # above it +-2 entries could push |sum| past 256
+GEMM_EXACT_MAX = {torch.bfloat16: 256, torch.float16: 2048}   # integers up to here: all exact
+GEMM_RES_MAX = 7
+GEMM_HQ = GEMM_HKV = 1
+GEMM_BS, GEMM_NB = 16, 32     # paged caches of the qkv cases: 512 slots
+GEMM_MAX_POS = 64
+GEMM_FP8_GATE_SHIFT = -5      # fp8 gate rows: scale * 2^-5 keeps |gate| <= 16 at scale 2
+E4M3_ONE, E4M3_TWO = 0x38, 0x40
+
+
+def gemm_exact_x(rows: int, k: int, norm: bool = False, seed: int = 1):
+    """fp32 [rows, k] of +-1; ``norm``: row m times 2^(m % 3), so mean(x^2) = 4^(m % 3)."""
+    g = torch.Generator().manual_seed(seed * 100003 + k)
+    x = (torch.randint(0, 2, (rows, k), generator=g) * 2 - 1).float()
+    if norm:
+        x = x * torch.pow(torch.tensor(2.0), (torch.arange(rows) % 3).float())[:, None]
+    return x
+
+
+def gemm_exact_w(n: int, k: int, seed: int = 2):
+    """int8 [n, k]: +-1, and +-2 on one entry in eight while k <= GEMM_TWO_MAG_MAX_K."""
+    g = torch.Generator().manual_seed(seed * 100003 + 31 * n + k)
+    w = torch.randint(0, 2, (n, k), generator=g) * 2 - 1
+    if k <= GEMM_TWO_MAG_MAX_K:
+        w = w * (1 + (torch.randint(0, 8, (n, k), generator=g) == 0).long())
+    return w.to(torch.int8)
+
+
+def gemm_fp8_scales(n: int):
+    """Row r: 2^((5 r) % 4 - 2): the 16 rows of any tile, under any row map, differ."""
+    return torch.pow(torch.tensor(2.0), ((5 * torch.arange(n)) % 4 - 2).float())
+
+
+def gemm_fp8_codes(w_int):
+    """e4m3fn bytes of an int8 tensor of +-1 / +-2, built directly."""
+    mag = torch.where(w_int.abs() == 2, E4M3_TWO, E4M3_ONE)
+    return (mag | torch.where(w_int < 0, 0x80, 0)).to(torch.uint8)
+
+
+@dataclass
+class GemmCase:
+    """Operands of one exact GEMM (CPU) in the weights' natural row order."""
+    epi: str                      # "plain" | "resadd" | "qkv" | "silu"
+    k: int
+    x: torch.Tensor               # fp32 [rows, k]
+    w_int: torch.Tensor           # int8 [n, k]
+    w: torch.Tensor               # fp32 [n, k]: w_int, gate rows of 16-bit silu cases / 16
+    wscale: torch.Tensor | None   # fp8: fp32 [n] row scales (w is then w_int)
+    res: torch.Tensor | None = None
+    pos: torch.Tensor | None = None
+    slots: torch.Tensor | None = None
+    table: torch.Tensor | None = None
+
+    @property
+    def norm(self):
+        return self.epi in ("qkv", "silu")
+
+    @property
+    def rowmap(self):
+        return self.epi if self.norm else "plain"
+
+    def ints(self):
+        """int64 [rows, n]: sum of sign(x) * w_int - what every stored value encodes."""
+        return (torch.sign(self.x).double() @ self.w_int.double().t()).long()
+
+    def cut(self, rows: int):
+        """The same case with only its first ``rows`` rows."""
+        f = lambda t: None if t is None else t[:rows]  # noqa: E731
+        return replace(self, x=self.x[:rows], res=f(self.res), pos=f(self.pos),
+                       slots=f(self.slots))
+
+
+def gemm_exact_case(epi: str, rows: int, n: int, k: int, fp8: bool = False) -> GemmCase:
+    """n: weight rows (qkv: (hq + 2 hkv) * 128 whatever is passed; silu: 2 * inter)."""
+    norm = epi in ("qkv", "silu")
+    if epi == "qkv":
+        n = (GEMM_HQ + 2 * GEMM_HKV) * 128
+    x = gemm_exact_x(rows, k, norm)
+    w_int = gemm_exact_w(n, k)
+    w = w_int.float()
+    wscale = gemm_fp8_scales(n) if fp8 else None
+    if epi == "silu":
+        if fp8:
+            wscale[: n // 2] *= 2.0 ** GEMM_FP8_GATE_SHIFT
+        else:
+            w[: n // 2] /= 16.0
+    c = GemmCase(epi=epi, k=k, x=x, w_int=w_int, w=w, wscale=wscale)
+    g = torch.Generator().manual_seed(7 * n + k)
+    if epi == "resadd":
+        c.res = torch.randint(-GEMM_RES_MAX, GEMM_RES_MAX + 1, (rows, n), generator=g).float()
+    if epi == "qkv":
+        assert rows <= GEMM_BS * GEMM_NB
+        c.pos = torch.randint(0, GEMM_MAX_POS, (rows,), generator=g, dtype=torch.int32)
+        c.slots = torch.randperm(GEMM_BS * GEMM_NB, generator=g)[:rows].to(torch.int32)
+        c.slots[min(1, rows - 1)] = -1           # a padding row writes no K / V
+        c.table = rope_exact_table(GEMM_MAX_POS, 128)
+    return c
+
+
+def gemm_sentinel(shape, dtype):
+    return torch.full(shape, ROW_SENTINEL, dtype=torch.int16).view(dtype)
+
+
+def gemm_exact_rounded64(c: GemmCase, dtype, inv_shift: int = 0):
+    """fp64 [rows, n]: T(acc * row scale * inv_rms), the first rounding of every epilogue.
+    ``inv_shift`` = 1: the wrong kernel that takes inv_rms from the next row."""
+    # exact even in fp32: every partial sum is a multiple of 2^-4 below 2^15
+    acc = (c.x @ c.w.t()).double()
+    if c.wscale is not None:
+        acc = acc * c.wscale.double()[None, :]
+    if c.norm:
+        inv = 1.0 / torch.sqrt((c.x.double() ** 2).mean(1) + float(np.float32(GEMM_EPS)))
+        acc = acc * torch.roll(inv, -inv_shift)[:, None]
+    return round_fmt(acc, dtype)[0]
+
+
+def gemm_exact_expected(c: GemmCase, dtype, rows: int | None = None, inv_shift: int = 0,
+                        rope_mutant: str | None = None, v_as_k: bool = False):
+    """What the kernels must store for the first ``rows`` rows, as a dict of tensors in
+    ``dtype``: "y" ([rows, n]; silu [rows, inter]; qkv: q [rows, hq * 128]), silu: "near";
+    qkv: "k" / "v", the WHOLE sentinel-filled caches after the launch.  The keyword arguments
+    build the wrong kernels test_wrong_references_are_caught must tell apart."""
+    m = c.x.shape[0] if rows is None else rows
+    y = gemm_exact_rounded64(c, dtype, inv_shift)[:m]
+    if c.epi == "plain":
+        return {"y": y.to(dtype)}
+    if c.epi == "resadd":
+        return {"y": round_fmt(y + c.res[:m].double(), dtype)[0].to(dtype)}
+    if c.epi == "silu":
+        out, near, _ = silu_ref64(y.to(dtype))
+        return {"y": out, "near": near}
+    kc = gemm_sentinel((GEMM_NB, GEMM_HKV, GEMM_BS, 128), dtype)
+    vc = gemm_sentinel((GEMM_NB, GEMM_HKV, 128, GEMM_BS), dtype)
+    q, _, kc, _, vc = rope_ref64(y.to(dtype), c.pos[:m], c.slots[:m], c.table, kc, vc, GEMM_HQ,
+                                 GEMM_HKV, 128, mutant=rope_mutant)
+    if v_as_k:  # one V element of the last live row lands where the K layout would put it
+        sl = int(c.slots[:m][c.slots[:m] >= 0][-1])
+        page, off, d = sl // GEMM_BS, sl % GEMM_BS, 5
+        val = vc[page, 0, d, off].clone()
+        vc[page, 0, d, off] = gemm_sentinel((1,), dtype)[0]
+        vc.view(GEMM_NB, GEMM_HKV, GEMM_BS, 128)[page, 0, off, d] = val
+    return {"y": q.reshape(m, -1), "k": kc, "v": vc}
+
+
+def gemm_mutate(c: GemmCase, name: str, rows: int):
+    """A copy of the case with operands changed the way a wrong kernel would read them (None:
+    the mutant does not apply to this case).  ``rows``: the live row count M."""
+    x, w, wi = c.x.clone(), c.w.clone(), c.w_int.clone()
+    ck = 128 if c.k % 128 == 0 else 32   # the prefill GEMM's K steps are 32 wide
+    nch = c.k // ck
+    n = w.shape[0]
+    if name.startswith("drop_"):       # drop_<first|mid|last>_<0|127>: one x element lost
+        _, chunk, el = name.split("_")
+        ch = {"first": 0, "mid": nch // 2, "last": nch - 1}[chunk]
+        x[rows - 1, ch * ck + min(int(el), ck - 1)] = 0
+    elif name == "chunk_slip":         # x chunk c meets weight chunk c + 1
+        if nch < 2:
+            return None
+        w, wi = torch.roll(w, -ck, 1), torch.roll(wi, -ck, 1)
+    elif name == "rows_across_16":
+        if rows < 17:
+            return None
+        x[[15, 16]] = x[[16, 15]]
+    elif name == "last_row_copy":      # the staged copy of row M - 1 leaks into row M - 2
+        if rows < 2:
+            return None
+        x[rows - 2] = x[rows - 1]
+    elif name == "w_rows_in_tile":
+        w[[0, 1]], wi[[0, 1]] = w[[1, 0]], wi[[1, 0]]
+    elif name == "w_tiles":
+        if n < 32:
+            return None
+        idx = torch.arange(n)
+        idx[:16], idx[16:32] = torch.arange(16, 32), torch.arange(16)
+        w, wi = w[idx], wi[idx]
+    elif name == "scale_rotate":       # fp8 scales rotated by one inside every 16-row tile
+        if c.wscale is None:
+            return None
+        s = torch.roll(c.wscale.reshape(-1, 16), 1, 1).reshape(-1)
+        return replace(c, wscale=s)
+    else:
+        raise ValueError(name)
+    return replace(c, x=x, w=w, w_int=wi)
+
+
+GEMM_OPERAND_MUTANTS = tuple(f"drop_{c}_{e}" for c in ("first", "mid", "last")
+                             for e in (0, 127)) + (
+    "chunk_slip", "rows_across_16", "last_row_copy", "w_rows_in_tile", "w_tiles", "scale_rotate")
+
+
+def gemm_slice_partials_max(c: GemmCase, s: int) -> int:
+    """Largest |partial sum| any of the s K slices (chunks [i nch / s, (i + 1) nch / s)) of any
+    output holds, as the integer it encodes."""
+    nch = c.k // 128
+    sx, wi = torch.sign(c.x).double(), c.w_int.double()
+    worst = 0
+    for i in range(s):
+        a, b = i * nch // s * 128, (i + 1) * nch // s * 128
+        worst = max(worst, int((sx[:, a:b] @ wi[:, a:b].t()).abs().max()))
+    return worst
