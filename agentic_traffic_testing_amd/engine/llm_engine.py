@@ -156,9 +156,23 @@ class LLMEngine:
         self.warmup_seconds = time.perf_counter() - t0
 
     # ------------------------------------------------------------------------------------
+    def check_sampling(self, sampling: SamplingParams) -> None:
+        """Raise ValueError for sampling parameters this engine cannot serve: a bad field
+        (``SamplingParams.check``, with this model's vocabulary bounding the logit_bias keys),
+        or a penalised request on a tensor-parallel engine - the token counts live in one
+        process's device memory; a TP group would need the state replicated per rank and a
+        seeding message to the workers."""
+        sampling.check(self.model_cfg.vocab_size)
+        if sampling.penalised and self.runner.tp_size > 1:
+            raise ValueError("presence_penalty, frequency_penalty, repetition_penalty and "
+                             "logit_bias are not served by a tensor-parallel engine")
+
     def add_request(self, request_id: str, prompt_ids, sampling: SamplingParams,
                     arrival_time: float | None = None) -> Sequence:
-        sampling.check()
+        self.check_sampling(sampling)
+        if sampling.penalised:
+            with self.lock:  # device state on first need - here, never inside a graph capture
+                self.runner.ensure_penalty_state()
         ids = list(map(int, prompt_ids))
         if not ids:
             ids = [self.tokenizer.bos_token_id]
@@ -175,7 +189,12 @@ class LLMEngine:
 
     def abort(self, request_id: str):
         with self.lock:
-            self.scheduler.abort(request_id)
+            for seq in self.scheduler.abort(request_id):
+                self.runner.penalty_release(seq.seq_id)
+
+    def _finish(self, seq: Sequence, reason: str) -> None:
+        self.scheduler.finish(seq, reason)
+        self.runner.penalty_release(seq.seq_id)  # (a no-op for an unpenalised sequence)
 
     def has_unfinished(self) -> bool:
         return self.scheduler.has_work() or self._inflight is not None
@@ -198,6 +217,8 @@ class LLMEngine:
                 ts = time.perf_counter()
                 with roctx.range("engine.schedule"):
                     batch = self.scheduler.schedule()
+                for seq in batch.preempted:  # re-seeded from its outputs when it comes back
+                    self.runner.penalty_release(seq.seq_id)
                 if batch.empty:
                     return []
                 t0 = time.perf_counter()
@@ -277,7 +298,7 @@ class LLMEngine:
             if reason:
                 del seq.output_ids[idx + 1:]  # drop a look-ahead placeholder
                 seq._ids_np = None
-                self.scheduler.finish(seq, reason)
+                self._finish(seq, reason)
             outs.append(self._output(seq, [tok], upto=idx + 1))
         self._account(cur.batch, len(outs), now - cur.t0)
         self.timing["post"] += time.perf_counter() - now
@@ -324,7 +345,7 @@ class LLMEngine:
                 self.runner.bm.commit(seq.seq_id, seq.token_array(), seq.num_computed)
                 reason = self._stop_reason(seq, tok)
                 if reason:
-                    self.scheduler.finish(seq, reason)
+                    self._finish(seq, reason)
                 outs.append(self._output(seq, [tok]))
             self._account(batch, len(outs), now - t0)
             self.timing["post"] += time.perf_counter() - now
@@ -346,6 +367,8 @@ class LLMEngine:
             return None  # a top-k / top-p row: the whole step samples through that kernel
         if any(seq.sampling.logprobs is not None for seq in batch.seqs):
             return None  # logprobs come from plain decode steps (verify rows record none)
+        if r._penalised(batch):
+            return None  # a verify row's counts would depend on which drafts are accepted
         max_kv = r.verify_max_kv(S)
         if any(seq.num_tokens > max_kv for seq in batch.seqs):
             return None
@@ -399,7 +422,7 @@ class LLMEngine:
                     seq.first_token_time = now
                 self.runner.bm.commit(seq.seq_id, seq.token_array(), seq.num_computed)
                 if reason:
-                    self.scheduler.finish(seq, reason)
+                    self._finish(seq, reason)
                 outs.append(self._output(seq, new))
                 n_new += len(new)
             self._account(vb, n_new, now - t0)

@@ -43,11 +43,15 @@ def _even(n: int) -> int:
 class MetaLayout:
     """int32-word layout of the packed per-step metadata buffer."""
 
-    def __init__(self, T: int, S: int, W: int, NT: int, R: int | None = None):
+    def __init__(self, T: int, S: int, W: int, NT: int, R: int | None = None,
+                 penalty: bool = False):
         # R: rows the sampler runs over - one per sequence, or every row of a verify step
         # (speculative decoding), whose sampling fields are row-sized
+        # penalty: a step of a penalty variant (V_PENALTY) carries four more per-row fields
+        # behind the others; every other step's layout is what it was without them
         R = S if R is None else R
         self.T, self.S, self.W, self.NT, self.R = T, S, W, NT, R
+        self.penalty = bool(penalty)
         o = 0
         self.fields = {}
 
@@ -74,6 +78,11 @@ class MetaLayout:
         add("logits_idx", R, torch.int64)
         add("seeds", R, torch.int64)
         add("steps", R, torch.int64)
+        if penalty:
+            add("pen_slot", R)                  # row of the penalty state; < 0: row unpenalised
+            add("pen_rep", R, torch.float32)    # repetition / frequency / presence penalty
+            add("pen_freq", R, torch.float32)
+            add("pen_pres", R, torch.float32)
         self.size = _even(o)
 
     def views(self, buf: torch.Tensor) -> dict:
@@ -107,18 +116,20 @@ OP_STEP, OP_CAPTURE, OP_STOP, OP_BARRIER = 1, 2, 3, 4
 
 # step variant (header word 8, third part of a graph key, word 3 of OP_CAPTURE): bit 0 - some
 # row samples with top-k / top-p (logits materialised); bits 1-2 - the logprob mode of the
-# step's most demanding sequence
+# step's most demanding sequence; bit 3 - some sequence has a penalty or a logit bias (logits
+# materialised, penalised into an fp32 buffer before the sampler, token counts updated after)
 V_TOPKP = 1
+V_PENALTY = 8
 LP_NONE, LP_SAMPLED, LP_TOPN = 0, 1, 2   # no logprobs / the sampled token's / + the top-N
 TOP_N = ops.MAX_TOP_LOGPROBS             # a top-N step computes this many; requests cut theirs
 
 
-def variant_code(topkp: bool, lp_mode: int) -> int:
-    return int(bool(topkp)) | (lp_mode << 1)
+def variant_code(topkp: bool, lp_mode: int, penalty: bool = False) -> int:
+    return int(bool(topkp)) | (lp_mode << 1) | (V_PENALTY if penalty else 0)
 
 
 def variant_lp(variant: int) -> int:
-    return variant >> 1
+    return (variant >> 1) & 3
 
 
 class ModelRunner:
@@ -223,7 +234,8 @@ class ModelRunner:
         self.bm = BlockManager(self.num_blocks, self.block_size, cfg.enable_prefix_caching)
         # metadata buffers (max layout)
         self.max_layout = MetaLayout(self.max_tokens, self.max_seqs, self.bt_width,
-                                     self.max_tokens, max(self.max_seqs, self.ws_rows))
+                                     self.max_tokens, max(self.max_seqs, self.ws_rows),
+                                     penalty=True)
         pin = self.is_cuda
         # two pinned metadata buffers, used alternately: a step's H2D copy may still be queued
         # while the host packs the next step (async look-ahead decode, TP workers); an event
@@ -303,6 +315,75 @@ class ModelRunner:
         self.verify_steps = 0
         self.timing = {"graph_prep": 0.0, "graph_run": 0.0}
         self._verify_rows: int | None = None
+        # sampling penalties (SamplingParams.penalised): device state allocated with the first
+        # such request (ensure_penalty_state), one row ("slot") per penalised running sequence
+        self.pen: dict | None = None
+        self._pen_slot: dict[int, int] = {}   # seq_id -> slot (seeded)
+        self._pen_free: list[int] = []
+
+    # -- sampling penalties ------------------------------------------------------------------
+    def ensure_penalty_state(self) -> None:
+        """Allocate the penalty state on first need - never inside a graph capture (the engine
+        calls this when a penalised request is added), never for an engine without one:
+        int32 [max_num_seqs, vocab] token words (bit 31: in the prompt, bits 0-30: times
+        generated), the [max_num_seqs, 300] bias tables and the fp32 logits buffer the apply
+        kernel writes and the sampler reads."""
+        if self.pen is not None:
+            return
+        if self.tp_size > 1:
+            raise ValueError("sampling penalties and logit_bias are not served under tensor "
+                             "parallelism")
+        n, V, dev = self.cfg.max_num_seqs, self.mcfg.vocab_size, self.device
+        nb = ops.PENALTY_BIAS_ENTRIES
+        self.pen = {
+            "state": torch.zeros(n, V, dtype=torch.int32, device=dev),
+            "bias_ids": torch.full((n, nb), -1, dtype=torch.int32, device=dev),
+            "bias_vals": torch.zeros(n, nb, dtype=torch.float32, device=dev),
+            "logits": torch.empty(self.max_seqs, V, dtype=torch.float32, device=dev),
+        }
+        self._pen_free = list(range(n - 1, -1, -1))
+
+    def _penalty_slot(self, seq) -> int:
+        """The slot of a penalised sequence whose next token this step samples; a sequence
+        without one (just admitted, or re-admitted after a preemption) gets a free slot, seeded
+        on the current stream from its prompt and the tokens it has generated so far."""
+        slot = self._pen_slot.get(seq.seq_id)
+        if slot is None:
+            if not self._pen_free:  # running sequences <= max_num_seqs, each holds at most one
+                raise RuntimeError("no free penalty slot: a finished, aborted or preempted "
+                                   "sequence was not released")
+            slot = self._pen_free.pop()
+            sp, pen = seq.sampling, self.pen
+            bias = sp.logit_bias or {}
+            ops.penalty_seed(pen["state"][slot], seq.prompt_ids, seq.output_ids,
+                             pen["bias_ids"][slot], pen["bias_vals"][slot],
+                             list(bias.keys()), [float(b) for b in bias.values()])
+            self._pen_slot[seq.seq_id] = slot
+        return slot
+
+    def penalty_release(self, seq_id: int) -> None:
+        """Give a finished, aborted or preempted sequence's slot back (host bookkeeping only;
+        nothing is launched).  The slot's device row is NOT touched here, and kernels already
+        queued may still read or count into it - safe, because every step, every seed and every
+        graph replay is ordered on one stream and the next owner's first use of the slot is its
+        seed, which zeroes the row and rewrites the bias table:
+
+        * a look-ahead step's update of a sequence that stopped on EOS one step earlier: step
+          n + 1 was queued with the slot before the host saw step n's EOS; its apply reads and
+          its update increments a row nobody owns any more, and its token is discarded by the
+          engine.  Any seed of that slot is queued after step n + 1, so it zeroes the stray count.
+        * a slot re-used by the next request: the new owner's seed is queued behind every step
+          that carried the old owner, so those steps saw the old counts and the new owner's
+          first apply sees exactly its seed.
+        * an abort in flight: the same - the in-flight steps finish against the old row, their
+          tokens are dropped (``_collect`` skips finished sequences), and the row is only handed
+          on through a later seed.
+
+        A preempted sequence comes back through ``_penalty_slot``, which re-seeds from its prompt
+        and all its outputs so far, so its counts continue across the recompute."""
+        slot = self._pen_slot.pop(seq_id, None)
+        if slot is not None:
+            self._pen_free.append(slot)
 
     def _room_for_decode_copies(self) -> bool:
         """The pre-shuffled decode copies double the 16-bit weights (16 GB for Llama-3.1-8B);
@@ -402,7 +483,8 @@ class ModelRunner:
         T = d["positions"].shape[0]
         S = d["seq_kvlen"].shape[0]
         NT = d["tile_seq"].shape[0]
-        lay = MetaLayout(T, S, self.bt_width, NT)
+        penalty = self._penalised(batch)
+        lay = MetaLayout(T, S, self.bt_width, NT, penalty=penalty)
         input_ids = np.zeros(T, dtype=np.int32)
         row = 0
         temps = np.zeros(S, dtype=np.float32)
@@ -421,6 +503,23 @@ class ModelRunner:
         arrays = dict(d)
         arrays.update(input_ids=input_ids, temperature=temps, top_p=top_p, top_k=top_k,
                       seeds=seeds, steps=steps, feed_prev=np.zeros(1, dtype=np.int32))
+        if penalty:
+            # per sampled row: the sequence's slot - only where this step samples its next
+            # token (a chunk short of the prompt's end has its sample dropped: no slot, no
+            # count); unpenalised and padded rows carry -1 and are copied through
+            self.ensure_penalty_state()
+            slot = np.full(S, -1, dtype=np.int32)
+            rep = np.ones(S, dtype=np.float32)
+            freq = np.zeros(S, dtype=np.float32)
+            pres = np.zeros(S, dtype=np.float32)
+            for i, (seq, s0, n) in enumerate(zip(batch.seqs, batch.q_start, batch.q_len)):
+                sp = seq.sampling
+                if sp.penalised and s0 + n == seq.num_tokens:
+                    slot[i] = self._penalty_slot(seq)
+                    rep[i] = sp.repetition_penalty
+                    freq[i] = sp.frequency_penalty
+                    pres[i] = sp.presence_penalty
+            arrays.update(pen_slot=slot, pen_rep=rep, pen_freq=freq, pen_pres=pres)
         return lay, arrays
 
     @property
@@ -475,15 +574,23 @@ class ModelRunner:
         """One step's forward + sampling.  ``variant`` (variant_code): bit 0 - some row uses
         top-p / top-k (logits are materialised and the top-k / top-p kernel samples every
         row); bits 1-2 - the step's logprob mode, whose results land in ws["lp"] (and
-        ws["top_ids"] / ws["top_lp"]), one row per sampled row."""
+        ws["top_ids"] / ws["top_lp"]), one row per sampled row; bit 3 - some sequence is
+        penalised (logits materialised, ``LlamaModel.sample_logits``' penalty tail)."""
         m = self.model
         T = v["input_ids"].shape[0]
         special = bool(variant & V_TOPKP)
         lp_mode = variant_lp(variant)
         lp_fused = self._lp_fusable(variant)
-        # logits are materialised for top-k / top-p and for every logprob the fused sampler
-        # cannot record
-        mat = special or (lp_mode != LP_NONE and not lp_fused)
+        # penalty variant: the materialised logits go through ops.penalty_apply into the fp32
+        # buffer, the sampler reads that, ops.penalty_update counts its tokens (logprobs stay
+        # on the raw logits)
+        pen = None
+        if variant & V_PENALTY:
+            pen = {**self.pen, "slot": v["pen_slot"], "rep": v["pen_rep"],
+                   "freq": v["pen_freq"], "pres": v["pen_pres"]}
+        # logits are materialised for top-k / top-p, penalties and for every logprob the fused
+        # sampler cannot record
+        mat = special or pen is not None or (lp_mode != LP_NONE and not lp_fused)
         # alternatives a materialised logprob step computes (None: no logprobs)
         lp_top = None if lp_mode == LP_NONE else (TOP_N if lp_mode == LP_TOPN else 0)
         if (self.fused_decode and md.num_tiles == 0
@@ -496,7 +603,7 @@ class ModelRunner:
                                     ws, v["temperature"], v["seeds"], v["steps"],
                                     prev_tokens=self.ws["tokens"], feed_prev=v["feed_prev"],
                                     top_p=v["top_p"] if special else None, top_k=v["top_k"],
-                                    lp_top=lp_top, lp_fused=lp_fused)
+                                    lp_top=lp_top, lp_fused=lp_fused, penalty=pen)
         decode_only = md.num_tiles == 0 and md.num_decode == T
         # final norm on the sampled rows only (each sequence's last token)
         last = m.forward(v["input_ids"], md, self.k_layers, self.v_layers, self.part_out,
@@ -513,11 +620,9 @@ class ModelRunner:
         # look-ahead step's embed) reads the samples from there, so the captured sampler must
         # write them there too (a fresh tensor would leave the previous step's tokens behind)
         out = self.ws["tokens"][:logits.shape[0]] if decode_only else None
-        if special:
-            toks = ops.sample_topkp(logits, v["temperature"], v["top_p"], v["top_k"],
-                                    v["seeds"], v["steps"], out=out)
-        else:
-            toks = ops.sample(logits, v["temperature"], v["seeds"], v["steps"], out=out)
+        toks = m.sample_logits(logits, v["temperature"], v["seeds"], v["steps"],
+                               top_p=v["top_p"] if special else None, top_k=v["top_k"],
+                               out=out, penalty=pen)
         if lp_top is not None:
             m.logits_logprobs(logits, toks, lp_top, self.ws)
         return toks
@@ -557,9 +662,13 @@ class ModelRunner:
             return LP_NONE
         return LP_TOPN if max(want) > 0 else LP_SAMPLED
 
+    @staticmethod
+    def _penalised(batch: Batch) -> bool:
+        return any(s.sampling.penalised for s in batch.seqs)
+
     @classmethod
     def _variant(cls, batch: Batch) -> int:
-        return variant_code(cls._special(batch), cls._lp_mode(batch))
+        return variant_code(cls._special(batch), cls._lp_mode(batch), cls._penalised(batch))
 
     def _fetch_logprobs(self, variant: int, n: int):
         """Synchronous copy of a step's logprob arrays (eager steps, after the tokens')."""
@@ -821,7 +930,7 @@ class ModelRunner:
             self.graphs[key].replay()
             self.graph_steps += 1
             return io["out"]
-        lay = MetaLayout(T, S, W, NT)
+        lay = MetaLayout(T, S, W, NT, penalty=bool(variant & V_PENALTY))
         dev = self.meta_dev[:size]
         self._h2d(dev, size)
         v = lay.views(dev)
@@ -897,20 +1006,25 @@ class ModelRunner:
     def capture(self, bucket: int, parts: int | None = None, variant: int = 0):
         """Capture a decode step for `bucket` sequences whose contexts fit `parts` attention
         partitions (default: max_model_len) into a hipGraph; ``variant`` (variant_code): the
-        top-k / top-p sampler (logits materialised) and / or a logprob mode.  Variants other
-        than 0 are captured on first use."""
+        top-k / top-p sampler (logits materialised), a logprob mode and / or the penalty tail.
+        Variants other than 0 are captured on first use."""
         variant = int(variant)
         parts = parts or self._tier(bucket)[1]
         if self.publisher is not None:
             hdr = np.zeros(HDR_WORDS, dtype=np.int32)
             hdr[0], hdr[1], hdr[2], hdr[3] = OP_CAPTURE, bucket, parts, variant
             self.publisher.publish(hdr)
-        lay = MetaLayout(bucket, bucket, self.bt_width, 0)
+        penalty = bool(variant & V_PENALTY)
+        if penalty:
+            self.ensure_penalty_state()  # (allocated with the request: a no-op here)
+        lay = MetaLayout(bucket, bucket, self.bt_width, 0, penalty=penalty)
         dev = torch.zeros(lay.size, dtype=torch.int32, device=self.device)
         v = lay.views(dev)
         # dummy sequences: kvlen 0, slot -1 -> kernels skip them
         v["seq_qstart"].copy_(torch.arange(bucket + 1, dtype=torch.int32))
         v["slot_mapping"].fill_(-1)
+        if penalty:  # no penalty slot either: the warm-up and capture passes count nothing
+            v["pen_slot"].fill_(-1)
         v["logits_idx"].copy_(torch.arange(bucket, dtype=torch.int64))
         md = self._meta(v, bucket, 0)
         # a capture may come between look-ahead steps (a new partition bucket mid-generation):
@@ -1007,5 +1121,5 @@ class ModelRunner:
 
 
 __all__ = ["ModelRunner", "MetaLayout", "ref", "HDR_WORDS", "OP_STEP", "OP_CAPTURE", "OP_STOP",
-           "OP_BARRIER", "LP_NONE", "LP_SAMPLED", "LP_TOPN", "TOP_N", "variant_code",
+           "OP_BARRIER", "LP_NONE", "LP_SAMPLED", "LP_TOPN", "TOP_N", "V_PENALTY", "variant_code",
            "variant_lp"]

@@ -3,6 +3,7 @@ from __future__ import annotations
 
 import enum
 import itertools
+import math
 import time
 from dataclasses import dataclass, field
 
@@ -10,6 +11,7 @@ import numpy as np
 
 
 MAX_LOGPROBS = 20  # most alternatives per position (ops.MAX_TOP_LOGPROBS)
+MAX_LOGIT_BIAS = 300  # most logit_bias entries per request (ops.PENALTY_BIAS_ENTRIES)
 
 
 @dataclass
@@ -30,15 +32,62 @@ class SamplingParams:
     # rounded to the model dtype, before temperature, Gumbel noise and top-k / top-p (vLLM's
     # default "raw_logprobs").  Tokens do not depend on this field.
     logprobs: int | None = None
+    # Penalties and bias (defaults: off).  For a sampled row, per token v, from the raw logit l
+    # in fp32:  1. v occurs in the prompt or the tokens generated so far -> l = l / rep if l > 0
+    # else l * rep;  2. c = times v was generated (the prompt does not count): l -= freq * c,
+    # l -= pres * (c > 0);  3. l += logit_bias[v].  Temperature, noise and top-k / top-p run on
+    # the result; logprobs stay raw.
+    presence_penalty: float = 0.0      # in [-2, 2]
+    frequency_penalty: float = 0.0     # in [-2, 2]
+    repetition_penalty: float = 1.0    # > 0
+    logit_bias: dict | None = None     # {token id: bias in [-100, 100]}, <= 300 entries
 
-    def check(self) -> None:
+    @property
+    def penalised(self) -> bool:
+        """Does any penalty or bias field differ from "off"?"""
+        return (self.presence_penalty != 0.0 or self.frequency_penalty != 0.0
+                or self.repetition_penalty != 1.0 or bool(self.logit_bias))
+
+    def check(self, vocab_size: int | None = None) -> None:
         """Raise ValueError for a field the engine cannot serve (called when a request is
-        added)."""
+        added, where the vocabulary size that bounds the logit_bias keys is known)."""
         lp = self.logprobs
         if lp is not None and (isinstance(lp, bool) or not isinstance(lp, int)
                                or not 0 <= lp <= MAX_LOGPROBS):
             raise ValueError(f"logprobs must be None or an integer in 0 .. {MAX_LOGPROBS}, "
                              f"got {lp!r}")
+        for name in ("presence_penalty", "frequency_penalty"):
+            v = getattr(self, name)
+            if not _is_number(v) or not -2.0 <= v <= 2.0:
+                raise ValueError(f"{name} must be a finite number in [-2, 2], got {v!r}")
+        v = self.repetition_penalty
+        if not _is_number(v) or not v > 0.0:
+            raise ValueError(f"repetition_penalty must be a finite number > 0, got {v!r}")
+        lb = self.logit_bias
+        if lb is None:
+            return
+        if not isinstance(lb, dict):
+            raise ValueError(f"logit_bias must be None or a dict of token id -> bias, got {lb!r}")
+        if len(lb) > MAX_LOGIT_BIAS:
+            raise ValueError(f"logit_bias takes at most {MAX_LOGIT_BIAS} entries, got {len(lb)}")
+        for k, b in lb.items():
+            if isinstance(k, bool) or not isinstance(k, int) or k < 0 \
+                    or (vocab_size is not None and k >= vocab_size):
+                bound = "" if vocab_size is None else f" in 0 .. {vocab_size - 1}"
+                raise ValueError(f"logit_bias keys must be integer token ids{bound}, got {k!r}")
+            if not _is_number(b) or not -100.0 <= b <= 100.0:
+                raise ValueError(f"logit_bias values must be finite numbers in [-100, 100], "
+                                 f"got {b!r} for token {k}")
+
+
+def _is_number(v) -> bool:
+    """A finite int or float; bools are not numbers here."""
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+        return False
+    try:
+        return math.isfinite(v)
+    except OverflowError:  # an int too large for a float
+        return False
 
 
 class SeqStatus(enum.Enum):

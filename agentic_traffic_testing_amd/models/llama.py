@@ -549,7 +549,7 @@ class LlamaModel:
                        temperature, seeds, steps, prev_tokens=None,
                        feed_prev=None, top_p=None, top_k=None, max_qlen: int = 1,
                        min_qlen: int = 1, lp_top: int | None = None,
-                       lp_fused: bool = False) -> torch.Tensor:
+                       lp_fused: bool = False, penalty: dict | None = None) -> torch.Tensor:
         """Fused decode step; returns sampled ids, one per row.  Every sequence has one query
         row - or, in a verify step of speculative decoding (``max_qlen`` > 1: the longest of
         the batch), sequence s of ``md.num_decode`` has the rows ``md.seq_qstart[s]`` ..
@@ -569,7 +569,10 @@ class LlamaModel:
         ws["lp"] - with ``lp_fused`` from the fused LM head + sampler's logprob epilogue (same
         launch count, tokens bit-identical to the plain step's), else from the materialised
         logits through ``ops.token_logprobs`` with its ``lp_top`` alternatives in
-        ws["top_ids"] / ws["top_lp"]."""
+        ws["top_ids"] / ws["top_lp"].
+
+        ``penalty`` (see ``sample_logits``): the logits are materialised as for top-k / top-p
+        and sampled through the penalty tail; logprobs still read the raw logits."""
         eps = self.cfg.rms_norm_eps
         nq, nkv = self.n_heads, self.n_kv_heads
         B = input_ids.shape[0]
@@ -603,18 +606,38 @@ class LlamaModel:
             ops.decode_gate_up_silu(residual, eps=eps, out=act,
                                     **self._decode_w(L, "gate_up", B))
             self._row_parallel(act, L, "down", residual)
-        if top_p is not None or (lp_top is not None and not lp_fused):
+        if top_p is not None or penalty is not None or (lp_top is not None and not lp_fused):
             logits = self.compute_logits(ops.rms_norm(residual, self.norm, eps))
-            if top_p is not None:
-                toks = ops.sample_topkp(logits, temperature, top_p, top_k, seeds, steps,
-                                        out=ws["tokens"][:B])
-            else:
-                toks = ops.sample(logits, temperature, seeds, steps, out=ws["tokens"][:B])
+            toks = self.sample_logits(logits, temperature, seeds, steps, top_p=top_p,
+                                      top_k=top_k, out=ws["tokens"][:B], penalty=penalty)
             if lp_top is not None:
                 self.logits_logprobs(logits, toks, lp_top, ws)
             return toks
         return self.sample_rows(residual, eps, temperature, seeds, steps, ws,
                                 logprobs=lp_top is not None)
+
+    @staticmethod
+    def sample_logits(logits: torch.Tensor, temperature, seeds, steps, top_p=None, top_k=None,
+                      out=None, penalty: dict | None = None) -> torch.Tensor:
+        """Sample one token per materialised ``logits`` row: the top-k / top-p kernel with
+        ``top_p`` (per-row device tensors), else the plain sampler.  ``penalty`` (the runner's
+        penalty state plus this step's per-row "slot" / "rep" / "freq" / "pres"): the sampler
+        reads ``ops.penalty_apply``'s fp32 rows instead of the raw ones and
+        ``ops.penalty_update`` then counts the sampled tokens - apply, sample, update, all on
+        device-side parameters, so the tail is captured with the step."""
+        src = logits
+        if penalty is not None:
+            src = ops.penalty_apply(penalty["logits"][:logits.shape[0]], logits,
+                                    penalty["state"], penalty["slot"], penalty["rep"],
+                                    penalty["freq"], penalty["pres"], penalty["bias_ids"],
+                                    penalty["bias_vals"])
+        if top_p is not None:
+            toks = ops.sample_topkp(src, temperature, top_p, top_k, seeds, steps, out=out)
+        else:
+            toks = ops.sample(src, temperature, seeds, steps, out=out)
+        if penalty is not None:
+            ops.penalty_update(penalty["state"], penalty["slot"], toks)
+        return toks
 
     @staticmethod
     def logits_logprobs(logits: torch.Tensor, toks: torch.Tensor, n_top: int, ws: dict) -> None:

@@ -1046,6 +1046,56 @@ def token_logprobs(logits, tokens, n_top: int = 0, out=None):
             top_lp.view(-1)[:rows * n_top].view(rows, n_top))
 
 
+PENALTY_BIAS_ENTRIES = ref.PENALTY_BIAS_ENTRIES  # logit_bias entries per slot (csrc/penalties.hip)
+
+
+def _i32(ids, device) -> torch.Tensor:
+    if isinstance(ids, torch.Tensor):
+        return ids.to(device=device, dtype=torch.int32).contiguous().view(-1)
+    return torch.tensor(list(ids), dtype=torch.int32).to(device)
+
+
+def penalty_seed(state_row, prompt_ids, output_ids, bias_ids_row, bias_vals_row,
+                 bias_ids=(), bias_vals=()):
+    """Reset one slot of the penalty state (csrc/penalties.hip): zero ``state_row`` [vocab]
+    int32, set bit 31 of every prompt token, add one per occurrence of every output token
+    (atomics: duplicates count), and write the slot's bias rows [300] (ids padded with -1).  The
+    id lists are sequences or int32 tensors; ids outside the vocabulary are skipped.  Ordered
+    on the current stream; called when a sequence is admitted, never on the decode path."""
+    if not state_row.is_cuda:
+        return ref.penalty_seed(state_row, prompt_ids, output_ids, bias_ids_row, bias_vals_row,
+                                bias_ids, bias_vals)
+    dev = state_row.device
+    b_ids = _i32(bias_ids, dev)
+    if isinstance(bias_vals, torch.Tensor):
+        b_vals = bias_vals.to(device=dev, dtype=torch.float32).contiguous().view(-1)
+    else:
+        b_vals = torch.tensor(list(bias_vals), dtype=torch.float32).to(dev)
+    _native().penalty_seed(state_row, bias_ids_row, bias_vals_row, _i32(prompt_ids, dev),
+                           _i32(output_ids, dev), b_ids, b_vals)
+
+
+def penalty_apply(out, logits, state, row_slot, rep, freq, pres, bias_ids, bias_vals):
+    """``out`` [R, V] fp32 <- the penalised logits of ``logits`` [R, V] (bf16 / fp16 / fp32, any
+    row stride): row r with slot s = row_slot[r] >= 0 reads state[s] (bit 31: in the prompt,
+    bits 0-30: times generated) - seen tokens are divided (l > 0) or multiplied by rep[r], then
+    l -= freq[r] * count + pres[r] * (count > 0), then the slot's bias entries are added; a row
+    with a negative slot is copied through.  One dense pass and one launch for the bias entries;
+    every parameter is a device tensor (graph-capturable)."""
+    if not logits.is_cuda:
+        return ref.penalty_apply(out, logits, state, row_slot, rep, freq, pres, bias_ids,
+                                 bias_vals)
+    _native().penalty_apply(out, logits, state, row_slot, rep, freq, pres, bias_ids, bias_vals)
+    return out
+
+
+def penalty_update(state, row_slot, tokens):
+    """count[row_slot[r], tokens[r]] += 1 for the rows with a slot (after the sampler)."""
+    if not state.is_cuda:
+        return ref.penalty_update(state, row_slot, tokens)
+    _native().penalty_update(state, row_slot, tokens)
+
+
 def decode_lm_head_sample(x, w, eps, temperature, seeds, steps, keys, tokens=None,
                           finalize=True, vocab_offset=0, preshuffled=False, logprobs=None,
                           lp_ws=None):

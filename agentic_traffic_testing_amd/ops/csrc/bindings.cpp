@@ -375,6 +375,134 @@ void token_logprobs(at::Tensor lp, at::Tensor top_ids, at::Tensor top_lp,
            "token_logprobs");
 }
 
+// ---- sampling penalties (penalties.hip) ------------------------------------------------------
+constexpr int64_t kPenBias = 300;  // bias entries per slot
+
+// state [slots, vocab] int32 contiguous, bias tables [slots, 300] int32 / fp32 contiguous, all
+// on one device
+void check_penalty_state(const at::Tensor& state, const at::Tensor& bias_ids,
+                         const at::Tensor& bias_vals, const char* op) {
+  check_dev(state, "state");
+  TORCH_CHECK(state.dim() == 2 && state.scalar_type() == at::kInt && state.is_contiguous(), op,
+              ": state must be a contiguous int32 [slots, vocab] tensor");
+  TORCH_CHECK(state.size(1) > 0 && state.size(1) <= (int64_t{1} << 30), op, ": vocab");
+  TORCH_CHECK(bias_ids.scalar_type() == at::kInt && bias_vals.scalar_type() == at::kFloat &&
+                  bias_ids.is_contiguous() && bias_vals.is_contiguous() && bias_ids.dim() == 2 &&
+                  bias_vals.dim() == 2 && bias_ids.size(0) == state.size(0) &&
+                  bias_vals.size(0) == state.size(0) && bias_ids.size(1) == kPenBias &&
+                  bias_vals.size(1) == kPenBias,
+              op, ": bias tables must be contiguous int32 / fp32 [slots, 300]");
+  TORCH_CHECK(bias_ids.device() == state.device() && bias_vals.device() == state.device(), op,
+              ": one device");
+}
+
+// state [vocab] int32, bias_ids [300] int32, bias_vals [300] fp32: one slot's rows
+void penalty_seed(at::Tensor state, at::Tensor bias_ids, at::Tensor bias_vals,
+                  const at::Tensor& prompt_ids, const at::Tensor& output_ids,
+                  const at::Tensor& new_bias_ids, const at::Tensor& new_bias_vals) {
+  check_dev(state, "state_row");
+  TORCH_CHECK(state.dim() == 1 && state.scalar_type() == at::kInt && state.is_contiguous() &&
+                  state.numel() > 0 && state.numel() <= (int64_t{1} << 30),
+              "penalty_seed: state_row must be a contiguous int32 [vocab] row");
+  TORCH_CHECK(bias_ids.scalar_type() == at::kInt && bias_vals.scalar_type() == at::kFloat &&
+                  bias_ids.is_contiguous() && bias_vals.is_contiguous() &&
+                  bias_ids.dim() == 1 && bias_vals.dim() == 1 && bias_ids.numel() == kPenBias &&
+                  bias_vals.numel() == kPenBias && bias_ids.device() == state.device() &&
+                  bias_vals.device() == state.device(),
+              "penalty_seed: bias rows must be contiguous int32 / fp32 [300] on the state's "
+              "device");
+  for (const at::Tensor* t : {&prompt_ids, &output_ids, &new_bias_ids})
+    TORCH_CHECK(t->scalar_type() == at::kInt && t->dim() == 1 && t->is_contiguous() &&
+                    (t->numel() == 0 || t->device() == state.device()),
+                "penalty_seed: id lists must be contiguous int32 vectors on the state's device");
+  TORCH_CHECK(new_bias_vals.scalar_type() == at::kFloat && new_bias_vals.is_contiguous() &&
+                  new_bias_vals.numel() == new_bias_ids.numel() &&
+                  (new_bias_vals.numel() == 0 || new_bias_vals.device() == state.device()),
+              "penalty_seed: bias values must be fp32, one per bias id");
+  TORCH_CHECK(new_bias_ids.numel() <= kPenBias, "penalty_seed: at most 300 bias entries, got ",
+              new_bias_ids.numel());
+  TORCH_CHECK(prompt_ids.numel() < (int64_t{1} << 31) && output_ids.numel() < (int64_t{1} << 31),
+              "penalty_seed: list length");
+  const int64_t vocab = state.numel();
+  const at::DeviceGuard g(state.device());
+  check_rc(atta_penalty_seed(state.data_ptr<int>(), static_cast<int>(vocab),
+                             prompt_ids.numel() ? prompt_ids.data_ptr<int>() : nullptr,
+                             static_cast<int>(prompt_ids.numel()),
+                             output_ids.numel() ? output_ids.data_ptr<int>() : nullptr,
+                             static_cast<int>(output_ids.numel()),
+                             bias_ids.data_ptr<int>(), bias_vals.data_ptr<float>(),
+                             new_bias_ids.numel() ? new_bias_ids.data_ptr<int>() : nullptr,
+                             new_bias_vals.numel() ? new_bias_vals.data_ptr<float>() : nullptr,
+                             static_cast<int>(new_bias_ids.numel()), cur_stream()),
+           "penalty_seed");
+}
+
+// The dense pass moves 4 elements per access where a row's logits, state and out pointers are
+// aligned for it, and goes element by element on any other row (an odd vocabulary, a column
+// slice): every element-aligned base and stride is served, so only a base that is not aligned to
+// its own element is refused here.
+void penalty_apply(at::Tensor out, const at::Tensor& logits, const at::Tensor& state,
+                   const at::Tensor& row_slot, const at::Tensor& rep, const at::Tensor& freq,
+                   const at::Tensor& pres, const at::Tensor& bias_ids,
+                   const at::Tensor& bias_vals) {
+  check_dev(logits, "logits");
+  check_penalty_state(state, bias_ids, bias_vals, "penalty_apply");
+  const int64_t rows = logits.dim() == 2 ? logits.size(0) : -1, vocab = state.size(1);
+  TORCH_CHECK(rows >= 0 && logits.size(1) == vocab && (vocab == 1 || logits.stride(1) == 1) &&
+                  logits.stride(0) >= 0,
+              "penalty_apply: logits [rows, vocab] with unit column stride");
+  TORCH_CHECK(out.dim() == 2 && out.scalar_type() == at::kFloat && out.size(0) == rows &&
+                  out.size(1) == vocab && (vocab == 1 || out.stride(1) == 1) &&
+                  (rows <= 1 || out.stride(0) >= vocab),
+              "penalty_apply: out must be fp32 [rows, vocab] with unit column stride");
+  int dt = 2;
+  if (logits.scalar_type() == at::kBFloat16) dt = 0;
+  else if (logits.scalar_type() == at::kHalf) dt = 1;
+  else TORCH_CHECK(logits.scalar_type() == at::kFloat, "penalty_apply: logits bf16 / fp16 / fp32");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % logits.element_size() == 0 &&
+                  reinterpret_cast<uintptr_t>(out.data_ptr()) % 4 == 0,
+              "penalty_apply: logits and out must start aligned to their element size");
+  TORCH_CHECK(row_slot.scalar_type() == at::kInt && rep.scalar_type() == at::kFloat &&
+                  freq.scalar_type() == at::kFloat && pres.scalar_type() == at::kFloat,
+              "penalty_apply: row_slot int32, rep / freq / pres fp32");
+  for (const at::Tensor* t : {&row_slot, &rep, &freq, &pres})
+    TORCH_CHECK(t->device() == logits.device(), "penalty_apply: one device");
+  TORCH_CHECK(state.device() == logits.device() && out.device() == logits.device(),
+              "penalty_apply: one device");
+  for (const at::Tensor* t : {&row_slot, &rep, &freq, &pres})
+    TORCH_CHECK(t->is_contiguous() && t->numel() >= rows, "penalty_apply: per-row arrays");
+  TORCH_CHECK(rows <= 65535, "penalty_apply: at most 65535 rows");
+  const at::DeviceGuard g(logits.device());
+  check_rc(atta_penalty_apply(out.data_ptr<float>(), rows > 1 ? out.stride(0) : vocab,
+                              logits.data_ptr(), rows > 1 ? logits.stride(0) : vocab, dt,
+                              state.data_ptr<int>(), static_cast<int>(rows),
+                              static_cast<int>(vocab), static_cast<int>(state.size(0)),
+                              row_slot.data_ptr<int>(), rep.data_ptr<float>(),
+                              freq.data_ptr<float>(), pres.data_ptr<float>(),
+                              bias_ids.data_ptr<int>(), bias_vals.data_ptr<float>(),
+                              cur_stream()),
+           "penalty_apply");
+}
+
+void penalty_update(at::Tensor state, const at::Tensor& row_slot, const at::Tensor& tokens) {
+  check_dev(state, "state");
+  TORCH_CHECK(state.dim() == 2 && state.scalar_type() == at::kInt && state.is_contiguous() &&
+                  state.size(1) <= (int64_t{1} << 30),
+              "penalty_update: state must be a contiguous int32 [slots, vocab] tensor");
+  TORCH_CHECK(row_slot.scalar_type() == at::kInt && tokens.scalar_type() == at::kLong &&
+                  row_slot.is_contiguous() && tokens.is_contiguous() &&
+                  row_slot.numel() >= tokens.numel() && tokens.numel() < (int64_t{1} << 31),
+              "penalty_update: row_slot int32 and tokens int64, one per row");
+  TORCH_CHECK(row_slot.device() == state.device() && tokens.device() == state.device(),
+              "penalty_update: one device");
+  const at::DeviceGuard g(state.device());
+  check_rc(atta_penalty_update(state.data_ptr<int>(), static_cast<int>(state.size(1)),
+                               static_cast<int>(state.size(0)), row_slot.data_ptr<int>(),
+                               tokens.data_ptr<int64_t>(), static_cast<int>(tokens.numel()),
+                               cur_stream()),
+           "penalty_update");
+}
+
 // fp8 weight-only quantisation: w is uint8 (OCP e4m3fn bytes, pre-shuffled in 16 x 64 blocks)
 // and w_scale the fp32 per-row dequant scale; returns the scale pointer (nullptr: 16-bit w).
 const float* fp8_scale(const at::Tensor& w, const c10::optional<at::Tensor>& w_scale,
@@ -1097,6 +1225,11 @@ TORCH_LIBRARY(atta, m) {
         "Tensor top_k, Tensor seeds, Tensor steps) -> ()");
   m.def("token_logprobs(Tensor(a!) lp, Tensor(b!) top_ids, Tensor(c!) top_lp, Tensor logits, "
         "Tensor tokens, int n_top) -> ()");
+  m.def("penalty_seed(Tensor(a!) state_row, Tensor(b!) bias_ids_row, Tensor(c!) bias_vals_row, "
+        "Tensor prompt_ids, Tensor output_ids, Tensor bias_ids, Tensor bias_vals) -> ()");
+  m.def("penalty_apply(Tensor(a!) out, Tensor logits, Tensor state, Tensor row_slot, Tensor rep, "
+        "Tensor freq, Tensor pres, Tensor bias_ids, Tensor bias_vals) -> ()");
+  m.def("penalty_update(Tensor(a!) state, Tensor row_slot, Tensor tokens) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(atta, CUDA, m) {
@@ -1117,6 +1250,9 @@ TORCH_LIBRARY_IMPL(atta, CUDA, m) {
   m.impl("sample", &sample);
   m.impl("sample_topkp", &sample_topkp);
   m.impl("token_logprobs", &token_logprobs);
+  m.impl("penalty_seed", &penalty_seed);
+  m.impl("penalty_apply", &penalty_apply);
+  m.impl("penalty_update", &penalty_update);
   m.impl("skinny_gemm", &skinny_gemm);
   m.impl("prefill_gemm", &prefill_gemm);
   m.impl("fused_qkv_rope", &fused_qkv_rope);

@@ -65,6 +65,21 @@ int atta_token_logprobs(float* lp, int* top_ids, float* top_lp, const void* logi
                         const int64_t* tokens, int rows, int vocab, int64_t stride,
                         int logits_is_fp32, int n_top, hipStream_t stream);
 
+// sampling penalties over device-resident token counts (penalties.hip): state [slots, vocab]
+// int32 (bit 31 prompt flag, bits 0-30 generated count), bias tables [slots, 300]
+int atta_penalty_seed(int* state_row, int vocab, const int* prompt_ids, int n_prompt,
+                      const int* output_ids, int n_output, int* bias_ids_row,
+                      float* bias_vals_row, const int* bias_ids, const float* bias_vals,
+                      int n_bias, hipStream_t stream);
+// logits_dtype: 0 bf16, 1 fp16, 2 fp32; rows with row_slot < 0 are copied through as fp32
+int atta_penalty_apply(float* out, int64_t out_stride, const void* logits, int64_t logits_stride,
+                       int logits_dtype, const int* state, int rows, int vocab, int num_slots,
+                       const int* row_slot, const float* rep, const float* freq,
+                       const float* pres, const int* bias_ids, const float* bias_vals,
+                       hipStream_t stream);
+int atta_penalty_update(int* state, int vocab, int num_slots, const int* row_slot,
+                        const int64_t* tokens, int rows, hipStream_t stream);
+
 int atta_skinny_gemm_push(const void* x, const void* w, int M, int N, int K, int64_t x_stride,
                           int waves, int ksplit, const float* wscale, int dtype,
                           void* const* bases, int rank, int world, int64_t max_elems,

@@ -185,6 +185,69 @@ def token_logprobs(logits: torch.Tensor, tokens: torch.Tensor, n_top: int = 0):
     return lp, order[:, :n_top].to(torch.int32), vals[:, :n_top].contiguous()
 
 
+# ---- sampling penalties over token counts (ops/csrc/penalties.hip) ---------------------------
+PENALTY_BIAS_ENTRIES = 300   # bias entries per slot
+PENALTY_PROMPT_BIT = -(1 << 31)   # bit 31 of an int32 state word: the token is in the prompt
+PENALTY_COUNT_MASK = 0x7FFFFFFF   # bits 0-30: times generated
+
+
+def penalty_seed(state_row: torch.Tensor, prompt_ids, output_ids, bias_ids_row: torch.Tensor,
+                 bias_vals_row: torch.Tensor, bias_ids=(), bias_vals=()) -> None:
+    """Reset one slot: ``state_row`` [vocab] int32 gets bit 31 for every prompt token and the
+    number of times each output token occurs in bits 0-30 (ids outside the vocabulary are
+    skipped); the slot's bias rows [300] get the entries, padded with id -1."""
+    V = state_row.shape[0]
+    state_row.zero_()
+    p = torch.as_tensor(prompt_ids, dtype=torch.long).view(-1)
+    p = p[(p >= 0) & (p < V)]
+    o = torch.as_tensor(output_ids, dtype=torch.long).view(-1)
+    o = o[(o >= 0) & (o < V)]
+    cnt = torch.bincount(o, minlength=V).to(torch.int32)
+    flag = torch.zeros(V, dtype=torch.int32)
+    flag[p] = PENALTY_PROMPT_BIT
+    state_row.copy_(cnt | flag)
+    n = len(bias_ids)
+    if n > PENALTY_BIAS_ENTRIES:
+        raise ValueError(f"penalty_seed: at most {PENALTY_BIAS_ENTRIES} bias entries, got {n}")
+    bias_ids_row.fill_(-1)
+    bias_vals_row.zero_()
+    if n:
+        bias_ids_row[:n] = torch.as_tensor(bias_ids, dtype=torch.int32)
+        bias_vals_row[:n] = torch.as_tensor(bias_vals, dtype=torch.float32)
+
+
+def penalty_apply(out: torch.Tensor, logits: torch.Tensor, state: torch.Tensor, row_slot,
+                  rep, freq, pres, bias_ids: torch.Tensor, bias_vals: torch.Tensor):
+    """fp32 penalised logits of each row r with slot s = row_slot[r] >= 0, per token v from the
+    raw logit l:  seen (prompt flag or count) -> l = l / rep if l > 0 else l * rep;
+    l -= freq * count;  l -= pres * (count > 0);  l += bias[v] if the slot's table has v.
+    Rows with a negative slot are the raw logits in fp32."""
+    lf = logits.float()
+    for r in range(lf.shape[0]):
+        s = int(row_slot[r])
+        l = lf[r].clone()
+        if s >= 0:
+            w = state[s]
+            c = (w & PENALTY_COUNT_MASK).float()
+            rp = rep[r].float()
+            l = torch.where(w != 0, torch.where(l > 0, l / rp, l * rp), l)
+            l = l - freq[r].float() * c
+            l = l - pres[r].float() * (c > 0).float()
+            ids = bias_ids[s]
+            ok = (ids >= 0) & (ids < l.shape[0])
+            l[ids[ok].long()] += bias_vals[s][ok]
+        out[r].copy_(l)
+    return out
+
+
+def penalty_update(state: torch.Tensor, row_slot, tokens) -> None:
+    """count[row_slot[r], tokens[r]] += 1 for every row with a slot."""
+    for r in range(tokens.shape[0]):
+        s, t = int(row_slot[r]), int(tokens[r])
+        if s >= 0 and 0 <= t < state.shape[1]:
+            state[s, t] += 1
+
+
 def lm_head_sample_logprobs(x: torch.Tensor, w: torch.Tensor, eps: float, temperature, seeds,
                             steps):
     """What the fused LM head + sampler with the logprob epilogue computes: the tokens of

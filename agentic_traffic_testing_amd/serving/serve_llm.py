@@ -3,7 +3,8 @@
 API-compatible with the reference's aiohttp front end over vLLM (llm/serve_llm.py):
 
 * ``POST /chat | /completion | /generate`` with ``{prompt|input, max_tokens?, request_id?,
-  system_prompt?, skip_chat_template?, logprobs?}`` -> ``{"output", "meta": {request_id,
+  system_prompt?, skip_chat_template?, logprobs?, presence_penalty?, frequency_penalty?,
+  repetition_penalty?, logit_bias?}`` -> ``{"output", "meta": {request_id,
   latency_ms, queue_wait_s, prompt_tokens, completion_tokens, total_tokens, otel}}`` (with an
   integer ``logprobs`` also ``"logprobs": {tokens, token_ids, token_logprobs,
   top_logprobs}``, one entry per generated token); 400 on bad JSON /
@@ -221,6 +222,17 @@ async def handle_chat(request: web.Request) -> web.Response:
             except ValueError as exc:
                 _leave()
                 return web.json_response({"error": str(exc)}, status=400)
+        # optional penalties and "logit_bias" (a JSON object: its keys are strings holding token
+        # ids); absent: nothing changes.  A bad value, or an engine that cannot serve them
+        # (tensor parallel), is a 400 with the engine's own message
+        try:
+            pen_kw = _penalty_fields(data)
+            if pen_kw:
+                check = getattr(st.engine, "check_sampling", None)
+                (check or SamplingParams.check)(SamplingParams(**pen_kw))
+        except ValueError as exc:
+            _leave()
+            return web.json_response({"error": str(exc)}, status=400)
         rid = request.headers.get("X-Request-ID") or data.get("request_id")
         request_id = str(rid) if rid else str(uuid.uuid4())[:8]
         span.set_attribute("app.request_id", request_id)
@@ -259,7 +271,7 @@ async def handle_chat(request: web.Request) -> web.Response:
 
         sp = SamplingParams(temperature=float(data.get("temperature", st.s.temperature)),
                             max_tokens=max(1, eff_new), ignore_eos=bool(data.get("ignore_eos", st.s.ignore_eos)),
-                            seed=data.get("seed"), logprobs=want_lp)
+                            seed=data.get("seed"), logprobs=want_lp, **pen_kw)
         queue_wait = 0.0
         final = None
         try:
@@ -359,6 +371,28 @@ async def handle_chat(request: web.Request) -> web.Response:
         if want_lp is not None:
             body["logprobs"] = _logprobs_body(st, final)
         return web.json_response(body)
+
+
+PENALTY_KEYS = ("presence_penalty", "frequency_penalty", "repetition_penalty")
+
+
+def _penalty_fields(data: dict) -> dict:
+    """The penalty keys of a request body as SamplingParams keyword arguments (absent or null
+    keys are left out; values are passed on as sent, for SamplingParams.check to judge).
+    ``logit_bias`` keys arrive as strings: each must hold an integer."""
+    kw = {k: data[k] for k in PENALTY_KEYS if data.get(k) is not None}
+    lb = data.get("logit_bias")
+    if lb is not None:
+        if not isinstance(lb, dict):
+            raise ValueError(f"logit_bias must be an object of token id -> bias, got {lb!r}")
+        bias = {}
+        for k, v in lb.items():
+            try:
+                bias[int(k.strip())] = v
+            except (AttributeError, ValueError):
+                raise ValueError(f"logit_bias keys must be integer token ids, got {k!r}") from None
+        kw["logit_bias"] = bias
+    return kw
 
 
 def _logprobs_body(st: ServerState, final) -> dict:

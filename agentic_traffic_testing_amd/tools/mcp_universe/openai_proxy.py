@@ -11,6 +11,9 @@ Same contract as reference tools/mcp_universe/openai_proxy.py:43-165:
 * ``logprobs: true`` (with an optional ``top_logprobs: k``) is forwarded as the backend's
   integer ``logprobs`` (``k`` or 0) and answered in ``choices[0].logprobs.content``; a request
   without it is forwarded exactly as before (not in the reference, which ignores both);
+* ``presence_penalty``, ``frequency_penalty``, ``logit_bias`` and vLLM's ``repetition_penalty``
+  are forwarded as sent when present (the backend validates them; its 400 comes back as the
+  502 above); requests without them are forwarded exactly as before;
 * ``GET /health`` and ``/ready`` report the backend URL; default port 8110.
 
 Deliberate fix (SURVEY §2.1 T5 notes the reference always returns null usage): when the
@@ -37,6 +40,8 @@ DEFAULT_BACKEND_URL = os.environ.get(BACKEND_URL_ENV, "http://llm-backend:8000/c
 EMPTY_OUTPUT = "[Proxy] Local LLM backend returned empty output."
 BACKEND_KEY = web.AppKey("backend_url", str)
 SESSION_KEY = web.AppKey("session", aiohttp.ClientSession)
+# forwarded to the backend as sent when present (repetition_penalty: vLLM's extension)
+PENALTY_KEYS = ("presence_penalty", "frequency_penalty", "repetition_penalty", "logit_bias")
 
 
 def flatten_messages(messages: t.Sequence[dict]) -> str:
@@ -123,6 +128,11 @@ async def handle_chat_completions(request: web.Request) -> web.Response:
     if want_lp:
         k = payload.get("top_logprobs")
         body["logprobs"] = k if isinstance(k, int) and not isinstance(k, bool) and k > 0 else 0
+    # OpenAI's penalties and logit_bias (and vLLM's repetition_penalty extension) go to the
+    # backend as sent - it validates them and answers 400; absent keys add nothing
+    for key in PENALTY_KEYS:
+        if payload.get(key) is not None:
+            body[key] = payload[key]
     url = request.app[BACKEND_KEY]
     try:
         async with request.app[SESSION_KEY].post(url, json=body) as resp:
