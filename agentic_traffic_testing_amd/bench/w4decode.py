@@ -12,9 +12,18 @@ Engine level: decode tokens/s over the steps after the prefill at B = 1, 5, 12, 
 alternating per repeat (8B: bf16, fp8, mxfp4 engines side by side; 70B: fp8 then mxfp4, one at a
 time - they do not fit together).
 
+Weights-only mode (``--wide`` / ``--ttft``, both off by default): per projection at M = 48, 96,
+128 the wide kernel's 4-bit builds against the 16-bit wide kernel on the pre-shuffled
+dequantised copy and against ``ops.expand_mxfp4`` + the library GEMM on the scratch, and the
+expand kernel alone in GB/s (0.53 B read + 2 B written per weight) - plain projections, the
+same interleaved rounds and cold weight rotation; and at engine level the time to the first
+token of an 85-row cached burst, a 475-row burst and a 3000-row prefill, a weights-only engine
+against a default-mode mxfp4 engine, alternating per repeat.
+
 One JSON object per line.  Needs a GPU.
 
     python -m agentic_traffic_testing_amd.bench.w4decode [--kernels 8b,70b] [--engines 8b,70b]
+        [--wide 8b,70b] [--ttft 8b]
 """
 from __future__ import annotations
 
@@ -119,6 +128,121 @@ def kernel_level(size: str, rounds: int, iters: int):
         torch.cuda.empty_cache()
 
 
+WIDE_ROWS = (48, 96, 128)
+
+
+def wide_level(size: str, rounds: int, iters: int):
+    """The 33-128-row routes of the weights-only mode, per projection (plain GEMM, bf16)."""
+    ops.ensure_splitk_workspace("cuda")
+    dt = torch.bfloat16
+    for proj, n, k in SHAPES[size]:
+        w4 = _weights("mxfp4", n, k, max(4, math.ceil(COLD_BYTES / (n * k * 4.25 / 8))))
+        w16 = _weights("bf16", n, k, max(4, math.ceil(COLD_BYTES / (n * k * 2))))
+        scratch = torch.empty(n, k, dtype=dt, device="cuda")
+        for m in WIDE_ROWS:
+            x = torch.randn(m, k, dtype=dt, device="cuda")
+            out = torch.empty(m, n, dtype=dt, device="cuda")
+            i4, i16 = [0], [0]
+
+            def next4():
+                i4[0] = (i4[0] + 1) % len(w4)
+                return w4[i4[0]][0], w4[i4[0]][1]["w_block_scale"]
+
+            def wide_w4():
+                wq, sq = next4()
+                ops.linear(x, wq, out=out, w_block_scale=sq, wide_w4=True)
+
+            def wide_16():
+                i16[0] = (i16[0] + 1) % len(w16)
+                ops.linear(x, w16[i16[0]][0], out=out, preshuffled=True)
+
+            def expand():
+                wq, sq = next4()
+                ops.expand_mxfp4(wq, sq, "plain", scratch)
+
+            def expand_lib():
+                expand()
+                torch.mm(x, scratch.t(), out=out)
+
+            calls = {"wide_w4": wide_w4, "wide_16": wide_16, "expand_lib": expand_lib,
+                     "expand": expand}
+            for name, fn in calls.items():  # warm: code objects, every copy touched
+                for _ in range((len(w16) if name == "wide_16" else len(w4)) + 2):
+                    fn()
+            torch.cuda.synchronize()
+            us = {name: [] for name in calls}
+            for _ in range(rounds):
+                for name, fn in calls.items():  # interleaved: one timing of each per round
+                    us[name].append(_time_us(fn, iters))
+            rec = {"level": "wide", "model": size, "proj": proj, "N": n, "K": k, "M": m,
+                   "rounds": rounds, "iters": iters}
+            for name in calls:
+                med = statistics.median(us[name])
+                rec[name] = {"us": round(med, 2), "min": round(min(us[name]), 2),
+                             "max": round(max(us[name]), 2)}
+            rec["expand"]["GBps"] = round(n * k * (4.25 / 8 + 2) / rec["expand"]["us"] / 1e3, 1)
+            rec["w4_vs_wide16"] = round(rec["wide_16"]["us"] / rec["wide_w4"]["us"], 3)
+            rec["w4_vs_expand_lib"] = round(rec["expand_lib"]["us"] / rec["wide_w4"]["us"], 3)
+            # slower than the fallback beyond this run's own spread of the fallback's number?
+            rec["w4_slower_than_expand_lib"] = bool(rec["wide_w4"]["us"] > rec["expand_lib"]["max"])
+            print(json.dumps(rec), flush=True)
+        del w4, w16, scratch
+        gc.collect()
+        torch.cuda.empty_cache()
+
+
+def _ttft_ms(eng, prompts):
+    sp = SamplingParams(temperature=0.0, max_tokens=1, ignore_eos=True)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    eng.generate(prompts, sp)
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def ttft_level(size: str, repeats: int):
+    """Time to the first token (one ``generate`` of one-token requests) of the three step
+    shapes the weights-only mode routes differently: an 85-row cached burst (5 requests of 17
+    new rows behind a cached 592-token prefix: the wide 4-bit kernels), a 475-row burst
+    (5 x 95 uncached rows) and a 3000-row prefill (both expand + library).  The default-mode
+    mxfp4 engine is the baseline; the two alternate per repeat on fresh random tokens."""
+    engs = {"default": _make_engine(size, "mxfp4", 2048),
+            "weights_only": _make_engine(size, "mxfp4", 2048, mxfp4_weights_only=True)}
+    vocab = min(engs["default"].model_cfg.vocab_size, 32000)
+    rng = np.random.default_rng(99)
+
+    def toks(n):
+        return rng.integers(1000, vocab, size=n).tolist()
+
+    def cases():
+        prefix = toks(592)
+        return {"cached_burst_85": (prefix, [prefix + toks(17) for _ in range(5)]),
+                "burst_475": (None, [toks(95) for _ in range(5)]),
+                "prefill_3000": (None, [toks(3000)])}
+
+    ms = {c: {e: [] for e in engs} for c in cases()}
+    for rep in range(-1, repeats):  # rep -1: warm-up, untimed
+        for case, (prefix, prompts) in cases().items():
+            for name, eng in engs.items():
+                eng.runner.reset_state()
+                if prefix is not None:
+                    _ttft_ms(eng, [prefix])  # leaves the prefix in the cache
+                t = _ttft_ms(eng, prompts)
+                if rep >= 0:
+                    ms[case][name].append(t)
+    for case, by in ms.items():
+        rec = {"level": "ttft", "model": size, "case": case, "repeats": repeats}
+        for name, xs in by.items():
+            rec[name] = {"ms": round(statistics.median(xs), 3), "min": round(min(xs), 3),
+                         "max": round(max(xs), 3)}
+        rec["weights_only_vs_default"] = round(rec["weights_only"]["ms"] / rec["default"]["ms"], 3)
+        print(json.dumps(rec), flush=True)
+    for name, eng in engs.items():
+        print(json.dumps({"level": "ttft", "model": size, "engine": name,
+                          "resident_weights": eng.runner.resident_weights,
+                          "memory_allocated": torch.cuda.memory_allocated()}), flush=True)
+
+
 def _decode_tok_s(eng, prompts, sps, tag: str):
     """Decode tokens/s over the steps after every request has its first token."""
     for i, (p, sp) in enumerate(zip(prompts, sps)):
@@ -134,14 +258,15 @@ def _decode_tok_s(eng, prompts, sps, tag: str):
     return (eng.total_generated - n0) / (time.perf_counter() - t0)
 
 
-def _make_engine(size: str, fmt: str, kv_blocks: int):
+def _make_engine(size: str, fmt: str, kv_blocks: int, **extra):
     from ..config import EngineConfig
     from ..engine.llm_engine import LLMEngine
 
     return LLMEngine(EngineConfig(
         model=MODELS[size], dtype="bfloat16", max_model_len=4096, max_num_seqs=12,
         max_num_batched_tokens=8192, use_graphs=True, seed=1234, device="cuda:0",
-        load_format="dummy", num_kv_blocks=kv_blocks, quantization="" if fmt == "bf16" else fmt))
+        load_format="dummy", num_kv_blocks=kv_blocks, quantization="" if fmt == "bf16" else fmt,
+        **extra))
 
 
 def _workload(eng, B: int, ctx: int, new_tokens: int):
@@ -207,6 +332,8 @@ def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--kernels", default="8b,70b", help="shape sets of the kernel level ('' off)")
     ap.add_argument("--engines", default="8b,70b", help="presets of the engine level ('' off)")
+    ap.add_argument("--wide", default="", help="shape sets of the 33-128-row level ('' off)")
+    ap.add_argument("--ttft", default="", help="presets of the weights-only TTFT level ('' off)")
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--iters", type=int, default=40)
     ap.add_argument("--batches", default="1,5,12")
@@ -218,6 +345,10 @@ def main(argv=None):
         raise SystemExit("bench/w4decode.py needs a GPU")
     for size in filter(None, a.kernels.split(",")):
         kernel_level(size, a.rounds, a.iters)
+    for size in filter(None, a.wide.split(",")):
+        wide_level(size, a.rounds, a.iters)
+    for size in filter(None, a.ttft.split(",")):
+        ttft_level(size, a.repeats)
     for size in filter(None, a.engines.split(",")):
         engine_level(size, [int(b) for b in a.batches.split(",")], a.context, a.new_tokens,
                      a.repeats)

@@ -264,6 +264,13 @@ class EngineConfig:
     # rows stream 4.25 bits per weight, larger steps run 16-bit copies of the quantised values.
     # Single GPU only
     quantization: str = ""
+    # quantization="mxfp4" only: hold the layer projections in 4 bits ALONE (4.25 bits per
+    # weight, no 16-bit copies; embedding, final norm and LM head stay 16-bit).  Steps of at most
+    # 32 rows run the 4-bit GEMV, 33-128 rows the wide kernel's 4-bit builds, every other step
+    # expands each projection into one shared 16-bit scratch just before its library GEMM
+    # (about 2.5 B of extra traffic per weight and step: why this is opt-in).  GPU only.
+    # --mxfp4-weights-only / LLM_MXFP4_WEIGHTS_ONLY
+    mxfp4_weights_only: bool = False
     num_kv_blocks: int = 0               # 0 = size from gpu_memory_utilization
     load_format: str = "auto"            # auto | dummy (random init) | safetensors
     # tensor parallelism: "auto" = RCCL ("nccl") on GPUs, gloo on CPU; "gloo" forces the
@@ -296,6 +303,9 @@ class EngineConfig:
         if self.quantization == "mxfp4" and self.tensor_parallel_size > 1:
             raise ValueError("quantization 'mxfp4' runs on one GPU: tensor_parallel_size "
                              f"= {self.tensor_parallel_size} is not supported with it")
+        if self.mxfp4_weights_only and self.quantization != "mxfp4":
+            raise ValueError("mxfp4_weights_only needs quantization='mxfp4' "
+                             f"(quantization={self.quantization!r})")
         if self.speculative not in ("", "ngram"):
             raise ValueError(f"speculative={self.speculative!r}: '' or 'ngram'")
         if self.speculative:
@@ -346,5 +356,8 @@ class EngineConfig:
             kw["spec_tokens"] = n
         if env.get("LLM_QUANTIZATION"):
             kw["quantization"] = env["LLM_QUANTIZATION"].strip().lower()
+        if env.get("LLM_MXFP4_WEIGHTS_ONLY"):
+            kw["mxfp4_weights_only"] = env["LLM_MXFP4_WEIGHTS_ONLY"].strip().lower() in (
+                "1", "true", "yes", "on")
         kw.update({k: v for k, v in overrides.items() if v is not None})
         return cfg.replace(**kw)

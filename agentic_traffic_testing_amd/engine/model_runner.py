@@ -146,7 +146,8 @@ class ModelRunner:
         self.publisher = None     # rank 0 of a TP group: ShmChannel to the workers
         t0 = time.perf_counter()
         self.model = LlamaModel(model_cfg, self.dtype, self.device, tp_rank, tp_size, comm,
-                                quantization=cfg.quantization)
+                                quantization=cfg.quantization,
+                                mxfp4_weights_only=cfg.mxfp4_weights_only)
         self.model.prefill_gemm = cfg.prefill_gemm
         self.model.prefill_gemm_min_rows = cfg.prefill_gemm_min_rows
         self.model.small_prefill_fused = cfg.small_prefill_fused
@@ -170,12 +171,20 @@ class ModelRunner:
                              or cfg.quantization == "fp8"):
             self.model.prepare_decode_weights()
         self.load_seconds = time.perf_counter() - t0
+        # device bytes of the weights by kind (LlamaModel.resident_weight_bytes)
+        self.resident_weights = self.model.resident_weight_bytes()
+        if cfg.mxfp4_weights_only:
+            rw = self.resident_weights
+            print(f"[atta] weights loaded in {self.load_seconds:.1f} s, resident: 4-bit codes "
+                  f"{rw['codes4'] / 2**30:.2f} GiB, block scales {rw['scales4'] / 2**30:.2f} GiB, "
+                  f"16-bit rest {rw['w16'] / 2**30:.2f} GiB, expand scratch "
+                  f"{rw['scratch'] / 2**30:.2f} GiB", flush=True)
         if self.is_cuda:
             # split-K GEMV workspace up front (32 MiB): a split chosen while a decode graph is
             # being captured (ATTA_DECODE_KSPLIT, TP shards) must not allocate inside the capture
             ops.ensure_splitk_workspace(self.device)
             if cfg.fused_decode:
-                ops.warm_wide_kernels(self.device, self.dtype)
+                ops.warm_wide_kernels(self.device, self.dtype, wide_w4=cfg.mxfp4_weights_only)
             if cfg.startup_warmup:
                 self.warm_library_gemms()
         self.block_size = cfg.block_size
@@ -729,7 +738,8 @@ class ModelRunner:
     def verify_rows(self) -> int:
         """Most rows (sequences + drafts) one verify step takes; 0: this runner cannot verify.
         On the GPU that is the largest row count the fused decode step runs (<= 128 rows on
-        pre-shuffled 16-bit weights, <= 32 on fp8 and mxfp4) inside the workspace; the CPU backend runs
+        pre-shuffled 16-bit weights, <= 32 on fp8 and mxfp4, <= 128 on mxfp4 weights-only with a
+        pre-shuffled LM head) inside the workspace; the CPU backend runs
         verify steps through the reference ops."""
         if self._verify_rows is None:
             rows = 0
@@ -740,7 +750,8 @@ class ModelRunner:
                     while ok and rows > 1 and not self.model.decode_step_fusable(rows):
                         rows -= 1
                     if self.model.quant == "mxfp4":  # verify steps stream the 4-bit copies
-                        rows = min(rows, ops.fused_max_rows(mxfp4=True))
+                        rows = min(rows, ops.fused_max_rows(mxfp4=True,
+                                                            wide_w4=self.model.w4_only))
                     rows = rows if ok and rows > 1 else 0
             self._verify_rows = rows
         return self._verify_rows
@@ -1089,6 +1100,11 @@ class ModelRunner:
         ws = {}
         for name in ("qkv", "o", "gate_up", "down"):
             w = getattr(L, name)
+            if w is None:
+                # mxfp4_weights_only: the library GEMMs read the expand scratch; for loading
+                # their code objects its current contents do as well as any
+                n_, k_ = self.model.proj_shape(L, name)
+                w = self.model.w4_scratch[:n_ * k_].view(n_, k_)
             ws[tuple(w.shape)] = (w, getattr(L, name + "_s"))
         ws.setdefault(tuple(self.model.lm_head.shape), (self.model.lm_head, None))
         pat = re.compile(r"^(\w+?)_TN,tn_(\d+)_(\d+)_(\d+)_")

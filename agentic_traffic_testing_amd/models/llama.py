@@ -36,6 +36,10 @@ DTYPES = {"bfloat16": torch.bfloat16, "bf16": torch.bfloat16, "float16": torch.f
           "float32": torch.float32, "fp32": torch.float32}  # fp32: CPU reference runs only
 
 
+# tile row map of each projection's 4-bit copy (ops.preshuffle_mxfp4)
+W4_ROWMAPS = {"qkv": "qkv", "o": "plain", "gate_up": "silu", "down": "plain"}
+
+
 def torch_dtype(name: str) -> torch.dtype:
     return DTYPES.get(str(name).replace("torch.", ""), torch.bfloat16)
 
@@ -58,11 +62,11 @@ class AttnMeta:
 @dataclass
 class LayerWeights:
     input_norm: torch.Tensor
-    qkv: torch.Tensor
-    o: torch.Tensor
+    qkv: torch.Tensor | None
+    o: torch.Tensor | None
     post_norm: torch.Tensor
-    gate_up: torch.Tensor
-    down: torch.Tensor
+    gate_up: torch.Tensor | None
+    down: torch.Tensor | None
     # decode copies in the GEMV's pre-shuffled layout (ops.preshuffle); None = use the
     # row-major weights above
     qkv_ps: torch.Tensor | None = None
@@ -77,7 +81,8 @@ class LayerWeights:
     down_s: torch.Tensor | None = None
     # MXFP4 weight-only quantisation (GPU): the projections above hold the dequantised 16-bit
     # values; these are the 4-bit decode copies (ops.preshuffle_mxfp4: packed e2m1 codes) and
-    # their e8m0 block scales, streamed by steps of at most 32 rows
+    # their e8m0 block scales, streamed by steps of at most 32 rows.  mxfp4_weights_only: the
+    # four projections (and the *_ps copies) above are None - these are the only copy
     qkv_w4: torch.Tensor | None = None
     o_w4: torch.Tensor | None = None
     gate_up_w4: torch.Tensor | None = None
@@ -90,7 +95,8 @@ class LayerWeights:
 
 class LlamaModel:
     def __init__(self, cfg: ModelConfig, dtype=torch.bfloat16, device="cuda", tp_rank: int = 0,
-                 tp_size: int = 1, tp_group=None, quantization: str = ""):
+                 tp_size: int = 1, tp_group=None, quantization: str = "",
+                 mxfp4_weights_only: bool = False):
         # tp_group: parallel.comm.TPComm (required when tp_size > 1)
         # quantization: "" (16-bit weights) | "fp8" (OCP e4m3fn weights, per-row scales; on the
         # CPU reference path the dequantised values are stored instead) | "mxfp4" (OCP
@@ -102,6 +108,16 @@ class LlamaModel:
         if quantization == "mxfp4" and tp_size > 1:
             raise ValueError("quantization 'mxfp4' runs on one GPU: tensor parallelism is not "
                              "supported with it")
+        # mxfp4_weights_only: each layer is quantised as it is made and keeps its 4-bit copies
+        # alone (no 16-bit projection survives _make_layer); steps without a 4-bit kernel
+        # expand a projection into self.w4_scratch just before its GEMM.  GPU only.
+        if mxfp4_weights_only and quantization != "mxfp4":
+            raise ValueError("mxfp4_weights_only needs quantization 'mxfp4'")
+        if mxfp4_weights_only and torch.device(device).type != "cuda":
+            raise ValueError("mxfp4_weights_only needs a GPU: the CPU reference computes with "
+                             "the dequantised 16-bit weights")
+        self.w4_only = bool(mxfp4_weights_only)
+        self.w4_scratch = None  # [max N * K] 16-bit, allocated once at load
         self.quant = quantization
         # prefill projections: "hipblaslt" (torch / hipBLASLt GEMMs) or "atta" (the
         # hand-written CDNA4 GEMM, ops/csrc/prefill_gemm.hip) for >= prefill_gemm_min_rows rows
@@ -182,6 +198,7 @@ class LlamaModel:
                                                 norm_w(base + 8)))
             del wq, wk, wv, wo, wg, wu, wd
         self._fold_final_norm()
+        self._alloc_w4_scratch()
         return self
 
     def _shard_rows(self, w: torch.Tensor, rows: int) -> torch.Tensor:
@@ -221,10 +238,87 @@ class LlamaModel:
             amax = (wo.float().abs().amax(1) if full else None,
                     wd.float().abs().amax(1) if full else None)
             return self._quantize_layer(ones, qkv, o, gu, down, amax)
+        if self.w4_only:
+            # 4 bits only: quantise, lay out for the kernels, drop the 16-bit tensor - one at a
+            # time, so the peak is this layer's 16-bit weights, not the model's
+            L = LayerWeights(ones, None, None, ones, None, None)
+            for proj, w in (("qkv", qkv), ("o", o), ("gate_up", gu), ("down", down)):
+                wq, sq = ops.preshuffle_mxfp4(*ops.quantize_mxfp4(w), W4_ROWMAPS[proj])
+                setattr(L, proj + "_w4", wq)
+                setattr(L, proj + "_b4", sq)
+            return L
         if self.quant == "mxfp4":  # the values MXFP4 can represent, in 16 bits
             qkv, o, gu, down = (ops.dequantize_mxfp4(*ops.quantize_mxfp4(w), self.dtype)
                                 for w in (qkv, o, gu, down))
         return LayerWeights(ones, qkv, o, ones, gu, down)
+
+    # -- mxfp4_weights_only ----------------------------------------------------------------
+    def proj_shape(self, L: LayerWeights, proj: str) -> tuple[int, int]:
+        """(N, K) of a layer projection, whichever copies exist."""
+        w = getattr(L, proj)
+        if w is not None:
+            return tuple(w.shape)
+        wq = getattr(L, proj + "_w4")
+        return wq.shape[0], wq.shape[1] * 2
+
+    def _alloc_w4_scratch(self):
+        """The one 16-bit scratch of the weights-only mode: the largest projection's N * K
+        values, shared by every layer and projection (a step expands into it in stream order,
+        just before the GEMM that reads it).  Allocated once at load."""
+        if self.w4_only and self.layers:
+            n = max(math.prod(self.proj_shape(self.layers[0], p)) for p in sp.PROJS)
+            self.w4_scratch = torch.empty(n, dtype=self.dtype, device=self.device)
+
+    def _w16(self, L: LayerWeights, proj: str) -> torch.Tensor:
+        """The row-major 16-bit weight of a projection for a library / prefill GEMM: the stored
+        tensor, or (weights-only mode) the 4-bit copy expanded into the shared scratch - valid
+        until the next call."""
+        w = getattr(L, proj)
+        if w is not None:
+            return w
+        if self.w4_scratch is None:
+            raise RuntimeError("mxfp4_weights_only: no 16-bit scratch (weights not loaded?)")
+        n, k = self.proj_shape(L, proj)
+        return ops.expand_mxfp4(getattr(L, proj + "_w4"), getattr(L, proj + "_b4"),
+                                W4_ROWMAPS[proj], self.w4_scratch[:n * k].view(n, k))
+
+    def dense_weight(self, layer_index: int, proj: str) -> torch.Tensor:
+        """The exact 16-bit values of a layer projection ("qkv" | "o" | "gate_up" | "down",
+        norm weights folded in) as a new row-major tensor - for tests and tools that need a
+        dense copy (tests/helpers.dense_logits) of a model that keeps none."""
+        L = self.layers[layer_index]
+        w = getattr(L, proj)
+        if w is not None and L.qkv_s is None:
+            return w.clone()
+        if getattr(L, proj + "_w4") is None:
+            raise ValueError("dense_weight: 16-bit or MXFP4 weights only")
+        codes, scales = ops.unshuffle_mxfp4(getattr(L, proj + "_w4"), getattr(L, proj + "_b4"),
+                                            W4_ROWMAPS[proj])
+        return ops.dequantize_mxfp4(codes, scales, self.dtype)
+
+    def resident_weight_bytes(self) -> dict:
+        """Bytes of weights held on the device, by kind: "codes4" (MXFP4 codes), "scales4"
+        (their block scales), "fp8" (bytes + row scales), "w16" (every 16-bit tensor:
+        embedding, norms, LM head, projections and pre-shuffled copies), "scratch"."""
+        def nb(ts):
+            seen, n = set(), 0
+            for t in ts:
+                if t is not None and t.data_ptr() not in seen:
+                    seen.add(t.data_ptr())
+                    n += t.numel() * t.element_size()
+            return n
+
+        Ls = self.layers
+        main = [w for l in Ls for w in (l.qkv, l.o, l.gate_up, l.down, l.qkv_ps, l.o_ps,
+                                        l.gate_up_ps, l.down_ps)]
+        fp8 = [w for w in main if w is not None and w.dtype == torch.uint8]
+        fp8 += [w for l in Ls for w in (l.qkv_s, l.o_s, l.gate_up_s, l.down_s)]
+        w16 = [w for w in main if w is not None and w.dtype != torch.uint8]
+        w16 += [self.embed, self.norm, self.lm_head, self.lm_head_ps]
+        w16 += [w for l in Ls for w in (l.input_norm, l.post_norm)]
+        return {"codes4": nb(w for l in Ls for w in (l.qkv_w4, l.o_w4, l.gate_up_w4, l.down_w4)),
+                "scales4": nb(w for l in Ls for w in (l.qkv_b4, l.o_b4, l.gate_up_b4, l.down_b4)),
+                "fp8": nb(fp8), "w16": nb(w16), "scratch": nb([self.w4_scratch])}
 
     def _quantize_layer(self, ones, qkv, o, gu, down, amax=(None, None)) -> LayerWeights:
         """fp8 weight-only quantisation of the four projections (after norm folding)."""
@@ -280,6 +374,7 @@ class LlamaModel:
                 get(pre + "mlp.down_proj.weight"), get(pre + "input_layernorm.weight"),
                 get(pre + "post_attention_layernorm.weight")))
         self._fold_final_norm()
+        self._alloc_w4_scratch()
         return self
 
     def prepare_decode_weights(self, copies16: bool = True):
@@ -287,6 +382,9 @@ class LlamaModel:
         for the hipBLASLt prefill GEMMs): each wave load of the decode kernels then reads one
         contiguous 1 KiB instead of 16 rows x 64 B.  Costs one extra copy of the weights,
         which 288 GB of HBM affords (16 GB for Llama-3-8B).
+
+        mxfp4_weights_only: the layers hold their 4-bit copies already and get no 16-bit ones;
+        only the LM head is pre-shuffled.
 
         quantization="mxfp4" always builds the 4-bit copies as well (4.25 bits per weight on
         top: re-quantising the stored values returns the codes they came from);
@@ -298,8 +396,7 @@ class LlamaModel:
             for L in self.layers:
                 if L.qkv_w4 is not None:
                     continue
-                for proj, rowmap in (("qkv", "qkv"), ("o", "plain"), ("gate_up", "silu"),
-                                     ("down", "plain")):
+                for proj, rowmap in W4_ROWMAPS.items():
                     wq, sq = ops.preshuffle_mxfp4(*ops.quantize_mxfp4(getattr(L, proj)), rowmap)
                     setattr(L, proj + "_w4", wq)
                     setattr(L, proj + "_b4", sq)
@@ -307,6 +404,8 @@ class LlamaModel:
                 torch.cuda.synchronize(self.device)
                 return self
         for L in self.layers:
+            if L.qkv is None:  # mxfp4_weights_only: the LM head's copy alone
+                break
             if L.qkv_s is not None:  # fp8: 16-row x 64-col blocks of bytes
                 L.qkv_ps = ops.preshuffle_fp8(L.qkv, "qkv")
                 L.o_ps = ops.preshuffle_fp8(L.o)
@@ -324,7 +423,7 @@ class LlamaModel:
     def decode_copy_bytes(self) -> int:
         """Bytes ``prepare_decode_weights`` adds (one copy of every decode GEMV weight)."""
         ts = [self.lm_head] + [w for l in self.layers for w in (l.qkv, l.o, l.gate_up, l.down)]
-        return sum(t.numel() * t.element_size() for t in ts)
+        return sum(t.numel() * t.element_size() for t in ts if t is not None)
 
     # ---------------------------------------------------------------------------------
     def weight_bytes(self) -> int:
@@ -333,6 +432,9 @@ class LlamaModel:
         for l in self.layers:
             ts += [l.input_norm, l.qkv, l.o, l.post_norm, l.gate_up, l.down, l.qkv_s, l.o_s,
                    l.gate_up_s, l.down_s]
+            if l.qkv is None:  # mxfp4_weights_only: the 4-bit copies are what is streamed
+                ts += [l.qkv_w4, l.o_w4, l.gate_up_w4, l.down_w4, l.qkv_b4, l.o_b4,
+                       l.gate_up_b4, l.down_b4]
         return sum(t.numel() * t.element_size() for t in ts if t is not None)
 
     def _all_reduce(self, x: torch.Tensor) -> torch.Tensor:
@@ -382,7 +484,8 @@ class LlamaModel:
                     qkv = self._gemm8(plan.qkv, xq, xs, L.qkv, L.qkv_s, dt)
                 else:
                     x = ops.rms_norm(residual, L.input_norm, eps)
-                    qkv = ops.prefill_gemm(x, L.qkv) if plan.qkv == GEMM else ops.linear(x, L.qkv)
+                    wqkv = self._w16(L, "qkv")
+                    qkv = ops.prefill_gemm(x, wqkv) if plan.qkv == GEMM else ops.linear(x, wqkv)
                 q = ops.rope_cache(qkv, md.positions, md.slot_mapping, self.cos_sin,
                                    k_caches[li], v_caches[li], nq, nkv, D)
             attn = torch.empty_like(q)
@@ -417,10 +520,11 @@ class LlamaModel:
                 a = ops.silu_and_mul(self._gemm8(plan.gate_up, xq, xs, L.gate_up, L.gate_up_s, dt))
             else:
                 x = ops.rms_norm(residual, L.post_norm, eps)
+                wgu = self._w16(L, "gate_up")
                 if plan.gate_up == GEMM:
-                    a = ops.prefill_gemm(x, L.gate_up, ops.GEMM_SILU)
+                    a = ops.prefill_gemm(x, wgu, ops.GEMM_SILU)
                 else:
-                    a = ops.silu_and_mul(ops.linear(x, L.gate_up))
+                    a = ops.silu_and_mul(ops.linear(x, wgu))
             self._proj_residual(plan.down, a, L, "down", residual)
         if rows is not None:
             residual = residual.index_select(0, rows)
@@ -441,16 +545,21 @@ class LlamaModel:
     gemm_tuned = False  # set by the model runner when a tuned library table is loaded
 
     def _w4_rows(self, T: int) -> bool:
-        """Does a T-row step stream the MXFP4 copies (the 4-bit build of the 16-row-tile GEMV)?"""
+        """Does a T-row step stream the MXFP4 copies (the 4-bit build of the 16-row-tile GEMV;
+        mxfp4_weights_only: or the wide kernel's 4-bit builds)?"""
         return (self.quant == "mxfp4" and bool(self.layers) and self.layers[0].qkv_w4 is not None
-                and ops.fused_kernel(T, True, mxfp4=True) is not None)
+                and ops.fused_kernel(T, True, mxfp4=True, wide_w4=self.w4_only) is not None)
 
     def _decode_w(self, L: LayerWeights, proj: str, T: int) -> dict:
         """The weight arguments of a fused op for a T-row step: the 4-bit copy with its block
         scales, else the pre-shuffled copy (fp8: with its row scales), else the row-major
         weight."""
         if self._w4_rows(T):
-            return {"w": getattr(L, proj + "_w4"), "w_block_scale": getattr(L, proj + "_b4")}
+            return {"w": getattr(L, proj + "_w4"), "w_block_scale": getattr(L, proj + "_b4"),
+                    "wide_w4": self.w4_only}
+        if self.w4_only:
+            raise RuntimeError(f"mxfp4_weights_only: no 4-bit kernel runs a {T}-row fused "
+                               f"{proj} (the step plan sends such steps through the scratch)")
         ps = L.qkv_ps is not None
         return {"w": getattr(L, proj + "_ps") if ps else getattr(L, proj), "preshuffled": ps,
                 "w_scale": getattr(L, proj + "_s")}
@@ -470,7 +579,7 @@ class LlamaModel:
             gemm_tuned=self.gemm_tuned, prefill_gemm=self.prefill_gemm,
             prefill_gemm_min_rows=self.prefill_gemm_min_rows,
             small_prefill_fused=self.small_prefill_fused, fused_decode=self.fused_decode,
-            midm_routes=self.MIDM_ROUTES, pg_auto=self._PG_AUTO,
+            w4_only=self.w4_only, midm_routes=self.MIDM_ROUTES, pg_auto=self._PG_AUTO,
             pg_auto_untuned=self._PG_AUTO_UNTUNED, pg_splitk=self._PG_SPLITK,
             midm_fp8_rows=self.MIDM_FP8_ROWS, fp8_gate_up_wide_max=self.FP8_GATE_UP_WIDE_MAX,
             fp8_fused_max_rows=self.FP8_FUSED_MAX_ROWS))
@@ -488,7 +597,7 @@ class LlamaModel:
         sums) on the plan's backend."""
         if backend == FUSED:
             return self._row_parallel(x, L, proj, residual)
-        w = getattr(L, proj)
+        w = self._w16(L, proj)
         if backend == GEMM_SPLITK:
             return ops.prefill_gemm(x, w, ops.GEMM_RESADD, residual=residual, schedule="splitk")
         if self.tp_size > 1:
@@ -529,13 +638,14 @@ class LlamaModel:
         wide kernel's rows (past the fused push's rows the row-parallel sums take the IPC /
         RCCL all-reduce); the mid-M routes are measured at TP = 1 shapes only."""
         ps = bool(self.layers) and self.layers[0].qkv_ps is not None
-        return sp.proj_fusable(T, self._proj_dims_ok, self.tp_size, ps, self.quant)
+        return sp.proj_fusable(T, self._proj_dims_ok, self.tp_size, ps, self.quant, self.w4_only)
 
     def decode_step_fusable(self, B: int) -> bool:
         """Can ``forward_decode`` run B sequences?  It runs every projection fused (gate_up
         included, which loses to the library past the wide kernel's rows: MIDM_ROUTES) and
         ends in the fused LM head + sampler."""
         return (self.proj_fusable(B) and B <= min(ops.fused_max_rows(), ops.WIDE_ROWS)
+                and (not self.w4_only or self._w4_rows(B))
                 and self.sampler_fusable(B))
 
     def sampler_fusable(self, rows: int) -> bool:
@@ -658,8 +768,11 @@ class LlamaModel:
         if self._w4_rows(x.shape[0]):  # MXFP4: one GPU only
             ops.linear(x, getattr(L, proj + "_w4"), residual=residual,
                        waves=ops.decode_waves(proj, mxfp4=True), ksplit=None, proj=proj,
-                       w_block_scale=getattr(L, proj + "_b4"))
+                       w_block_scale=getattr(L, proj + "_b4"), wide_w4=self.w4_only)
             return
+        if self.w4_only:
+            raise RuntimeError(f"mxfp4_weights_only: no 4-bit kernel runs a {x.shape[0]}-row "
+                               f"fused {proj}")
         ps = L.qkv_ps is not None
         w = getattr(L, proj + "_ps") if ps else getattr(L, proj)
         scale = getattr(L, proj + "_s")

@@ -35,6 +35,9 @@ and ``fused_decode`` on, every projection's K in whole wave steps, ``ATTA_WIDE_M
 | fp8                  | any | the rest [4]       | lib   | lib         | lib [1]     | lib      |
 | mxfp4                | 1   | 1-32               | fused | fused       | fused       | fused    |
 | mxfp4                | 1   | the rest [5]       | as the 16-bit rows above                      |
+| mxfp4, weights only  | 1   | 1-32               | fused | fused       | fused       | fused    |
+| mxfp4, weights only  | 1   | 33-128 [6]         | fused | fused       | fused       | fused    |
+| mxfp4, weights only  | 1   | the rest [6]       | expand + the "16-bit, the rest" row           |
 
 [1] no tuned library table loaded: ``gemm`` from 2048 rows (bf16) / 2560 rows (fp8).
 [2] no tuned library table loaded, TP = 1, bf16: ``gemm_splitk`` at 448-1152 rows.
@@ -47,6 +50,12 @@ and ``fused_decode`` on, every projection's K in whole wave steps, ``ATTA_WIDE_M
 [5] ``quantization="mxfp4"`` keeps the projections dequantised in 16 bits, so a step past the
     4-bit GEMV's 32 rows is planned exactly as the same model without quantisation (pre-shuffled
     or row-major, whichever 16-bit copies exist); at most 32 rows stream the 4-bit copies.
+
+[6] ``mxfp4_weights_only`` holds the projections in 4 bits alone: 33-128 rows run the wide
+    kernel's 4-bit builds (``ops.fused_kernel(..., mxfp4=True, wide_w4=True)``); every other
+    step expands each projection into the model's shared 16-bit scratch (``ops.expand_mxfp4``)
+    just before its GEMM and is planned as the same model without quantisation and without
+    pre-shuffled copies (library GEMMs, ``gemm`` where [1] / [2] route it, rows padded).
 
 fp8 weights are always pre-shuffled on a GPU (without the copies no fp8 step runs fused).  With
 the fused path off (either switch, a K that is not whole wave steps, the kernel limits) a step
@@ -141,6 +150,7 @@ class StepFacts:
     prefill_gemm_min_rows: int = 128
     small_prefill_fused: bool = True
     fused_decode: bool = True
+    w4_only: bool = False       # mxfp4_weights_only: no 16-bit projections exist
     # the measured tables above
     midm_routes: dict = field(default_factory=lambda: MIDM_ROUTES)
     pg_auto: dict = field(default_factory=lambda: PG_AUTO)
@@ -179,11 +189,15 @@ def proj_dims_ok(gpu: bool, quant: str, hidden: int, q_width: int, inter: int) -
     return gpu and hidden % step == 0 and inter % step == 0 and q_width % step == 0
 
 
-def proj_fusable(T: int, dims_ok: bool, tp_size: int, preshuffled: bool, quant: str) -> bool:
+def proj_fusable(T: int, dims_ok: bool, tp_size: int, preshuffled: bool, quant: str,
+                 w4_only: bool = False) -> bool:
     """LlamaModel.proj_fusable."""
-    kernel = ops.fused_kernel(T, preshuffled, preshuffled and quant == "fp8")
-    if kernel is None and quant == "mxfp4":
-        kernel = ops.fused_kernel(T, True, mxfp4=True)
+    if w4_only:  # the 4-bit copies are all there is
+        kernel = ops.fused_kernel(T, True, mxfp4=True, wide_w4=True)
+    else:
+        kernel = ops.fused_kernel(T, preshuffled, preshuffled and quant == "fp8")
+        if kernel is None and quant == "mxfp4":
+            kernel = ops.fused_kernel(T, True, mxfp4=True)
     return dims_ok and (tp_size == 1 or T <= ops.WIDE_ROWS) and kernel is not None
 
 
@@ -211,8 +225,13 @@ def step_plan(T: int, f: StepFacts) -> StepPlan:
     """The plan of a T-row prefill / mixed step (the table in the module comment)."""
     if f.quant == "mxfp4":
         if (f.gpu and f.tp_size == 1 and f.small_prefill_fused and f.fused_decode and f.dims_ok
-                and ops.fused_kernel(T, True, mxfp4=True) is not None):
+                and ops.fused_kernel(T, True, mxfp4=True, wide_w4=f.w4_only) is not None):
             return StepPlan(FUSED, FUSED, FUSED, FUSED, fp8_chain=False, pad_rows=False)
+        if f.w4_only:
+            # expand + the plan of the unquantised model without pre-shuffled copies, library
+            # side only: a row-major GEMV would re-read the scratch it was just expanded into
+            return step_plan(T, replace(f, quant="", w4_only=False, preshuffled=False,
+                                        small_prefill_fused=False))
         return step_plan(T, replace(f, quant=""))
     fp8 = f.quant == "fp8" and f.gpu
     tp1 = f.tp_size == 1

@@ -411,7 +411,7 @@ def _policy_tops() -> tuple[int, int, int]:
 
 
 def fused_kernel(m: int, preshuffled: bool, fp8: bool = False, epi: str = "plain",
-                 mxfp4: bool = False) -> str | None:
+                 mxfp4: bool = False, wide_w4: bool = False) -> str | None:
     """Which hand-written weight-streaming kernel runs ``m`` rows over this weight layout with
     this epilogue ("plain" | "resadd" | "qkv" | "silu" | "sample" | "sample_lp" | "push";
     "sample_lp", the sampler with the logprob record, routes as "sample" does but has no fp8
@@ -419,14 +419,21 @@ def fused_kernel(m: int, preshuffled: bool, fp8: bool = False, epi: str = "plain
     16-row-tile GEMV), "wide", "midm", or None (no kernel: the native call would fail).  The
     routing table of csrc/gemv.hip ``route()`` (written out there and in docs/kernels.md)
     under the policy limits above.  ``mxfp4``: the 4-bit copies (``preshuffle_mxfp4``), which
-    only the 16-row-tile GEMV streams.  Pure: no native call, usable without a GPU."""
+    only the 16-row-tile GEMV streams - unless the caller chooses ``wide_w4``, the wide
+    kernel's 4-bit builds for 33-128 rows (the same keyword on ``linear`` /
+    ``decode_qkv_rope`` / ``decode_gate_up_silu``).  Pure: no native call, usable without a
+    GPU."""
     skinny_top, wide_top, midm_top = _policy_tops()
     if m < 1 or (epi == "sample_lp" and fp8):
         return None
     if epi == "sample_lp":
         epi = "sample"
     if mxfp4:
-        return "skinny" if m <= skinny_top and epi not in ("sample", "push") else None
+        if epi in ("sample", "push"):
+            return None
+        if m <= SKINNY_ROWS:
+            return "skinny" if m <= skinny_top else None
+        return "wide" if wide_w4 and m <= wide_top else None
     if not (preshuffled or fp8) or epi == "push" or not wide_top:
         return "skinny" if m <= skinny_top else None
     if m <= SKINNY_ROWS and (fp8 or m < _wide_min_rows[1 if epi == "silu" else 0]):
@@ -438,12 +445,15 @@ def fused_kernel(m: int, preshuffled: bool, fp8: bool = False, epi: str = "plain
     return "midm" if epi != "sample" and WIDE_ROWS < m <= midm_top else None
 
 
-def fused_max_rows(preshuffled: bool = True, mxfp4: bool = False) -> int:
+def fused_max_rows(preshuffled: bool = True, mxfp4: bool = False, wide_w4: bool = False) -> int:
     """Most rows a projection (any epilogue but the sampler's) may have to run on the
     hand-written weight-streaming kernels: row-major weights or the MXFP4 copies (the
-    16-row-tile GEMV alone), or pre-shuffled 16-bit / fp8."""
+    16-row-tile GEMV alone; with ``wide_w4`` the wide kernel's 4-bit builds too), or
+    pre-shuffled 16-bit / fp8."""
     tops = _policy_tops()
-    return max(tops) if preshuffled and not mxfp4 else tops[0]
+    if mxfp4:
+        return max(tops[:2]) if wide_w4 else tops[0]
+    return max(tops) if preshuffled else tops[0]
 
 
 SKINNY_WAVES = int(os.environ.get("ATTA_SKINNY_WAVES", "8"))
@@ -550,14 +560,16 @@ def _ksplit(proj: str, x: torch.Tensor, ksplit: int | None, tiles: int) -> int:
 
 
 def skinny_ok(x: torch.Tensor, w: torch.Tensor, preshuffled: bool = False,
-              fp8: bool = False, mxfp4: bool = False) -> bool:
+              fp8: bool = False, mxfp4: bool = False, wide_w4: bool = False) -> bool:
     """Does ``x @ w.T`` run on the hand-written MFMA kernels?  Shapes they take, and a row
     count ``fused_kernel`` names a kernel for.  ``mxfp4``: ``w`` holds the packed codes
-    [N, K / 2] of ``preshuffle_mxfp4``."""
+    [N, K / 2] of ``preshuffle_mxfp4``; ``wide_w4``: the caller chose the wide kernel's 4-bit
+    builds for 33-128 rows."""
     m, k = x.shape
     if mxfp4 and (w.dtype != torch.uint8 or w.shape[1] * 2 != k):
         return False
-    return (x.is_cuda and fused_kernel(m, preshuffled, fp8, mxfp4=mxfp4) is not None
+    return (x.is_cuda and fused_kernel(m, preshuffled, fp8, mxfp4=mxfp4,
+                                       wide_w4=wide_w4) is not None
             and w.shape[0] % 16 == 0 and k % 128 == 0 and x.stride(1) == 1
             and w.is_contiguous())
 
@@ -584,7 +596,7 @@ def midm_plan(m: int, ntiles: int, k: int, epi: int) -> tuple[int, int]:
 MIDM_BUILT = (3, 4, 5, 6, 8, 10, 12)  # row-block heights / 16 (csrc/midm_b<N>.hip)
 
 
-def warm_wide_kernels(device, dtype=torch.bfloat16) -> None:
+def warm_wide_kernels(device, dtype=torch.bfloat16, wide_w4: bool = False) -> None:
     """Launch one tiny GEMM from every translation unit of the wide (wide_mt<N>.hip: one per
     16-row block count the limits allow) and mid-M kernels (midm_b<N>.hip per row-block
     height, midm.hip's split-K reduce), so every code object is loaded at engine start: HIP
@@ -592,7 +604,8 @@ def warm_wide_kernels(device, dtype=torch.bfloat16) -> None:
     otherwise lands inside a timed prefill (1.5-2.5 ms per object: burst TTFT 4.7 -> 6.3 / 7.3
     ms the first time a 50 / 95-row burst ran, scripts/gpu/probe_fanout_ttft.py).  Only
     kernels the configured limits can route to are launched, and the caller's wide row
-    thresholds are restored afterwards."""
+    thresholds are restored afterwards.  ``wide_w4`` (the weights-only MXFP4 mode): the wide
+    kernel's 4-bit translation units (wide_w4_mt<N>.hip) and the expand kernel as well."""
     dev = torch.device(device)
     top = fused_max_rows()
     if dev.type != "cuda" or top <= SKINNY_MAX_M:
@@ -611,6 +624,13 @@ def warm_wide_kernels(device, dtype=torch.bfloat16) -> None:
                 linear(x, w, preshuffled=True)
             set_midm_plan(6, 2)  # the split-K reduce launch (midm.hip)
             linear(x, w, preshuffled=True)
+        if wide_w4:
+            wq = torch.zeros(128, 128, dtype=torch.uint8, device=dev)
+            sq = torch.full((128, 8), 127, dtype=torch.uint8, device=dev)
+            for rows in range(SKINNY_ROWS + 16, fused_max_rows(mxfp4=True, wide_w4=True) + 1, 16):
+                linear(torch.zeros(rows, 256, dtype=dtype, device=dev), wq, w_block_scale=sq,
+                       wide_w4=True)
+            expand_mxfp4(wq, sq, "plain", torch.empty(128, 256, dtype=dtype, device=dev))
     finally:
         set_wide_min_rows(*prev)
     torch.cuda.synchronize(dev)
@@ -719,6 +739,25 @@ def unshuffle_mxfp4(wq: torch.Tensor, sq: torch.Tensor, rowmap: str = "plain"
         inv[rows] = torch.arange(N, device=rows.device)
         codes, scales = codes.index_select(0, inv), scales.index_select(0, inv)
     return codes, scales
+
+
+ROWMAPS = {"plain": 0, "qkv": 1, "silu": 2}
+
+
+def expand_mxfp4(wq: torch.Tensor, sq: torch.Tensor, rowmap: str, out: torch.Tensor
+                 ) -> torch.Tensor:
+    """``out`` [N, K] bf16 / fp16 (row-major) := the 16-bit values of one projection's 4-bit
+    copy (``wq`` / ``sq`` of ``preshuffle_mxfp4`` with this ``rowmap``): bit for bit
+    ``dequantize_mxfp4(*unshuffle_mxfp4(wq, sq, rowmap), out.dtype)`` wherever every value is
+    a normal number of ``out.dtype`` (scale bytes 97..157 for bf16, 114..140 for fp16), with
+    the convert the 4-bit GEMMs use.  One streaming HIP kernel, no allocation: the
+    weights-only MXFP4 mode runs it into its scratch inside steps and graph captures."""
+    if rowmap not in ROWMAPS:
+        raise ValueError(f"unknown rowmap {rowmap}")
+    if not (out.is_cuda and wq.is_cuda and sq.is_cuda):
+        raise ValueError("expand_mxfp4 is a HIP kernel: GPU tensors only")
+    _native().expand_mxfp4(out, wq, sq, ROWMAPS[rowmap])
+    return out
 
 
 def _rowmap_index(N: int, rowmap: str, dev):
@@ -910,32 +949,36 @@ def linear(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor | None = Non
            out: torch.Tensor | None = None, waves: int | None = None,
            preshuffled: bool = False, w_scale: torch.Tensor | None = None,
            ksplit: int | None = 1, proj: str = "",
-           w_block_scale: torch.Tensor | None = None) -> torch.Tensor:
+           w_block_scale: torch.Tensor | None = None, wide_w4: bool = False) -> torch.Tensor:
     """y = x @ w.T.  With ``residual`` the product is added to ``residual`` IN PLACE and
     ``residual`` is returned (residual-stream update).  Decode-sized M runs the MFMA skinny
     GEMM; everything else (prefill, CPU) runs F.linear (hipBLASLt on the GPU).
     ``preshuffled``: ``w`` comes from ``preshuffle`` (skinny path only).
     ``w_scale``: ``w`` is fp8 (uint8, ``preshuffle_fp8`` layout) with this per-row scale.
     ``w_block_scale``: ``w`` / this are the MXFP4 codes / block scales of
-    ``preshuffle_mxfp4`` (at most 32 rows: the 16-row-tile GEMV alone streams them)."""
+    ``preshuffle_mxfp4`` (at most 32 rows: the 16-row-tile GEMV alone streams them - unless
+    ``wide_w4`` chooses the wide kernel's 4-bit builds for 33-128 rows)."""
     mxfp4 = w_block_scale is not None
+    wide_w4 = wide_w4 and mxfp4
     _need_cuda(x, preshuffled or w_scale is not None or mxfp4)
     fp8 = w_scale is not None
     if fp8 or mxfp4:
         preshuffled = True
-    fused = skinny_ok(x, w, preshuffled, fp8, mxfp4)
+    fused = skinny_ok(x, w, preshuffled, fp8, mxfp4, wide_w4)
     if preshuffled and not fused:
         raise ValueError("pre-shuffled weights need the skinny (decode) path")
     if fused:
         ksplit = _ksplit(proj, x, ksplit, w.shape[0] // 16)
+        if wide_w4:
+            ensure_splitk_workspace(x.device)  # the wide kernel plans its own split
         if residual is not None:
             _native().skinny_gemm(residual, x, w, residual, waves or SKINNY_WAVES, preshuffled,
-                                  w_scale, ksplit, w_block_scale)
+                                  w_scale, ksplit, w_block_scale, wide_w4)
             return residual
         if out is None:
             out = torch.empty(x.shape[0], w.shape[0], dtype=x.dtype, device=x.device)
         _native().skinny_gemm(out, x, w, None, waves or SKINNY_WAVES, preshuffled, w_scale,
-                              ksplit, w_block_scale)
+                              ksplit, w_block_scale, wide_w4)
         return out
     if residual is not None:
         # hipBLASLt C-matrix epilogue: residual = residual + x @ w.T in one GEMM (fp32
@@ -972,10 +1015,14 @@ def linear_push_reduce(x: torch.Tensor, w: torch.Tensor, residual: torch.Tensor,
 # ---- fused decode-step ops (norm weight folded into W on the host) -----------------------
 def decode_qkv_rope(x, w, eps, positions, slots, cos_sin, k_cache, v_cache, n_q_heads,
                     n_kv_heads, q_out=None, preshuffled=False, w_scale=None, ksplit=None,
-                    w_block_scale=None, waves=None):
+                    w_block_scale=None, waves=None, wide_w4=False):
     """RMSNorm(x) -> QKV GEMM -> RoPE -> q out + paged K/V write, one kernel on the GPU.
-    ``w_block_scale``: MXFP4 weights (``preshuffle_mxfp4``, row map "qkv")."""
+    ``w_block_scale``: MXFP4 weights (``preshuffle_mxfp4``, row map "qkv"); ``wide_w4``: as
+    ``linear``'s."""
     mxfp4 = w_block_scale is not None
+    wide_w4 = bool(wide_w4 and mxfp4 and x.is_cuda)
+    if wide_w4:
+        ensure_splitk_workspace(x.device)
     _need_cuda(x, preshuffled or w_scale is not None or mxfp4)
     check_slots(k_cache, slots[:x.shape[0]], "decode_qkv_rope")
     if q_out is None:
@@ -991,15 +1038,20 @@ def decode_qkv_rope(x, w, eps, positions, slots, cos_sin, k_cache, v_cache, n_q_
                              waves or decode_waves("qkv", preshuffled, w_scale is not None,
                                                    mxfp4=mxfp4),
                              preshuffled or w_scale is not None or mxfp4, w_scale,
-                             _ksplit("qkv", x, ksplit, w.shape[0] // 16), w_block_scale)
+                             _ksplit("qkv", x, ksplit, w.shape[0] // 16), w_block_scale,
+                             wide_w4)
     return q_out
 
 
 def decode_gate_up_silu(x, w, eps, out=None, preshuffled=False, w_scale=None, ksplit=None,
-                        w_block_scale=None, waves=None):
+                        w_block_scale=None, waves=None, wide_w4=False):
     """RMSNorm(x) -> gate_up GEMM -> SiLU(gate) * up, one kernel on the GPU.
-    ``w_block_scale``: MXFP4 weights (``preshuffle_mxfp4``, row map "silu")."""
+    ``w_block_scale``: MXFP4 weights (``preshuffle_mxfp4``, row map "silu"); ``wide_w4``: as
+    ``linear``'s."""
     mxfp4 = w_block_scale is not None
+    wide_w4 = bool(wide_w4 and mxfp4 and x.is_cuda)
+    if wide_w4:
+        ensure_splitk_workspace(x.device)
     _need_cuda(x, preshuffled or w_scale is not None or mxfp4)
     inter = w.shape[0] // 2
     if out is None:
@@ -1012,7 +1064,8 @@ def decode_gate_up_silu(x, w, eps, out=None, preshuffled=False, w_scale=None, ks
                                   mxfp4=mxfp4)
     _native().fused_gate_up_silu(out, x, w, eps, waves,
                                  preshuffled or w_scale is not None or mxfp4, w_scale,
-                                 _ksplit("gate_up", x, ksplit, w.shape[0] // 16), w_block_scale)
+                                 _ksplit("gate_up", x, ksplit, w.shape[0] // 16), w_block_scale,
+                                 wide_w4)
     return out
 
 

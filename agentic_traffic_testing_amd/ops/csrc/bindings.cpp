@@ -542,15 +542,16 @@ const uint8_t* mxfp4_scale(const at::Tensor& x, const at::Tensor& w,
   return w_block_scale->data_ptr<uint8_t>();
 }
 
-// dtype code for the skinny GEMV entry points; bit 8 flags pre-shuffled weights (kPreshuffled)
-int skinny_dtype(const at::Tensor& x, bool preshuffled) {
-  return dtype_code(x) | (preshuffled ? kPreshuffled : 0);
+// dtype code for the skinny GEMV entry points; bit 8 flags pre-shuffled weights (kPreshuffled),
+// bit 9 the caller's choice of the wide kernel's MXFP4 builds (kWideW4)
+int skinny_dtype(const at::Tensor& x, bool preshuffled, bool wide_w4 = false) {
+  return dtype_code(x) | (preshuffled ? kPreshuffled : 0) | (wide_w4 ? kWideW4 : 0);
 }
 
 void skinny_gemm(at::Tensor y, const at::Tensor& x, const at::Tensor& w,
                  const c10::optional<at::Tensor>& residual, int64_t waves, bool preshuffled,
                  const c10::optional<at::Tensor>& w_scale, int64_t ksplit,
-                 const c10::optional<at::Tensor>& w_block_scale) {
+                 const c10::optional<at::Tensor>& w_block_scale, bool wide_w4) {
   check_dev(x, "x");
   TORCH_CHECK(x.dim() == 2 && w.dim() == 2 && y.dim() == 2, "skinny_gemm: 2-D operands");
   TORCH_CHECK(x.stride(1) == 1 && y.stride(1) == 1 && w.is_contiguous(), "skinny_gemm: layout");
@@ -572,7 +573,7 @@ void skinny_gemm(at::Tensor y, const at::Tensor& x, const at::Tensor& w,
   const at::DeviceGuard g(x.device());
   check_rc(atta_skinny_gemm(y.data_ptr(), x.data_ptr(), w.data_ptr(), r, x.size(0), w.size(0),
                             x.size(1), x.stride(0), y.stride(0), rs, waves, ksplit, ws, bs,
-                            skinny_dtype(x, preshuffled), cur_stream()),
+                            skinny_dtype(x, preshuffled, wide_w4 && bs != nullptr), cur_stream()),
            "skinny_gemm");
 }
 
@@ -679,7 +680,8 @@ void fused_qkv_rope(at::Tensor q_out, at::Tensor k_cache, at::Tensor v_cache, co
                     const at::Tensor& w, const at::Tensor& positions, const at::Tensor& slots,
                     const at::Tensor& cos_sin, int64_t n_q_heads, int64_t n_kv_heads, double eps,
                     int64_t waves, bool preshuffled, const c10::optional<at::Tensor>& w_scale,
-                    int64_t ksplit, const c10::optional<at::Tensor>& w_block_scale) {
+                    int64_t ksplit, const c10::optional<at::Tensor>& w_block_scale,
+                    bool wide_w4) {
   const uint8_t* bs = mxfp4_scale(x, w, w_scale, w_block_scale, "fused_qkv_rope");
   check_skinny(x, w, "fused_qkv_rope", bs != nullptr);
   const float* ws = bs != nullptr ? nullptr : fp8_scale(w, w_scale, "fused_qkv_rope");
@@ -695,14 +697,15 @@ void fused_qkv_rope(at::Tensor q_out, at::Tensor k_cache, at::Tensor v_cache, co
                                slots.data_ptr<int>(), cos_sin.data_ptr<float>(), x.size(0),
                                x.size(1), x.stride(0), q_out.stride(0), n_q_heads, n_kv_heads,
                                k_cache.size(2), static_cast<float>(eps), waves, ksplit, ws, bs,
-                               skinny_dtype(x, preshuffled), cur_stream()),
+                               skinny_dtype(x, preshuffled, wide_w4 && bs != nullptr),
+                               cur_stream()),
            "fused_qkv_rope");
 }
 
 void fused_gate_up_silu(at::Tensor out, const at::Tensor& x, const at::Tensor& w, double eps,
                         int64_t waves, bool preshuffled,
                         const c10::optional<at::Tensor>& w_scale, int64_t ksplit,
-                        const c10::optional<at::Tensor>& w_block_scale) {
+                        const c10::optional<at::Tensor>& w_block_scale, bool wide_w4) {
   const uint8_t* bs = mxfp4_scale(x, w, w_scale, w_block_scale, "fused_gate_up_silu");
   check_skinny(x, w, "fused_gate_up_silu", bs != nullptr);
   const float* ws = bs != nullptr ? nullptr : fp8_scale(w, w_scale, "fused_gate_up_silu");
@@ -712,8 +715,39 @@ void fused_gate_up_silu(at::Tensor out, const at::Tensor& x, const at::Tensor& w
   check_rc(atta_fused_gate_up_silu(out.data_ptr(), x.data_ptr(), w.data_ptr(), x.size(0),
                                    x.size(1), out.size(1), x.stride(0), out.stride(0),
                                    static_cast<float>(eps), waves, ksplit, ws, bs,
-                                   skinny_dtype(x, preshuffled), cur_stream()),
+                                   skinny_dtype(x, preshuffled, wide_w4 && bs != nullptr),
+                                   cur_stream()),
            "fused_gate_up_silu");
+}
+
+// out [N, K] bf16 / fp16 (row-major, rows may be strided) := the MXFP4 weight wq / sq of
+// ops.preshuffle_mxfp4, dequantised, the tile row map (0 plain, 1 qkv, 2 silu) undone
+void expand_mxfp4(at::Tensor out, const at::Tensor& wq, const at::Tensor& sq, int64_t rowmap) {
+  check_dev(out, "out");
+  TORCH_CHECK(wq.is_cuda() && sq.is_cuda() && wq.device() == out.device() &&
+                  sq.device() == out.device(),
+              "expand_mxfp4: one GPU");
+  TORCH_CHECK(wq.scalar_type() == at::kByte && sq.scalar_type() == at::kByte && wq.dim() == 2 &&
+                  sq.dim() == 2 && wq.is_contiguous() && sq.is_contiguous(),
+              "expand_mxfp4: uint8 codes [N, K / 2] and block scales [N, K / 32]");
+  const int64_t N = wq.size(0), K = wq.size(1) * 2;
+  TORCH_CHECK(N >= 16 && N % 16 == 0 && K >= 128 && K % 128 == 0 && sq.size(0) == N &&
+                  sq.size(1) * 32 == K && N < (int64_t(1) << 31) && K < (int64_t(1) << 31),
+              "expand_mxfp4: N % 16 == 0, K % 128 == 0, scales [N, K / 32]");
+  TORCH_CHECK(rowmap >= 0 && rowmap <= 2 && (rowmap != 1 || N % 128 == 0),
+              "expand_mxfp4: rowmap 0 (plain) / 1 (qkv: whole 128-dim heads) / 2 (silu)");
+  TORCH_CHECK((out.scalar_type() == at::kBFloat16 || out.scalar_type() == at::kHalf) &&
+                  out.dim() == 2 && out.size(0) == N && out.size(1) == K && out.stride(1) == 1 &&
+                  out.stride(0) >= K && out.stride(0) % 8 == 0 &&
+                  reinterpret_cast<uintptr_t>(out.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(wq.data_ptr()) % 16 == 0 &&
+                  reinterpret_cast<uintptr_t>(sq.data_ptr()) % 4 == 0,
+              "expand_mxfp4: out must be bf16 / fp16 [N, K], rows 16-byte aligned");
+  const at::DeviceGuard g(out.device());
+  check_rc(atta_expand_mxfp4(out.data_ptr(), wq.data_ptr(), sq.data_ptr<uint8_t>(),
+                             static_cast<int>(N), static_cast<int>(K), out.stride(0),
+                             static_cast<int>(rowmap), dtype_code(out), cur_stream()),
+           "expand_mxfp4");
 }
 
 void fused_lm_head_sample(at::Tensor tokens, at::Tensor keys, const at::Tensor& x,
@@ -1164,10 +1198,11 @@ TORCH_LIBRARY(atta, m) {
       "fused_qkv_rope(Tensor(a!) q_out, Tensor(b!) k_cache, Tensor(c!) v_cache, Tensor x, "
       "Tensor w, Tensor positions, Tensor slots, Tensor cos_sin, int n_q_heads, int n_kv_heads, "
       "float eps, int waves, bool preshuffled=False, Tensor? w_scale=None, int ksplit=1, "
-      "Tensor? w_block_scale=None) -> ()");
+      "Tensor? w_block_scale=None, bool wide_w4=False) -> ()");
   m.def("fused_gate_up_silu(Tensor(a!) out, Tensor x, Tensor w, float eps, int waves, "
         "bool preshuffled=False, Tensor? w_scale=None, int ksplit=1, "
-        "Tensor? w_block_scale=None) -> ()");
+        "Tensor? w_block_scale=None, bool wide_w4=False) -> ()");
+  m.def("expand_mxfp4(Tensor(a!) out, Tensor wq, Tensor sq, int rowmap) -> ()");
   m.def("set_splitk_workspace(Tensor ws, Tensor counters) -> ()");
   m.def("quant_rows_fp8(Tensor(a!) q, Tensor(b!) scale, Tensor x, Tensor? w, int mode, "
         "float eps, Tensor(c!)? residual=None) -> ()");
@@ -1182,7 +1217,7 @@ TORCH_LIBRARY(atta, m) {
   m.def("sample_finalize(Tensor(a!) tokens, Tensor keys, int n_tiles) -> ()");
   m.def("skinny_gemm(Tensor(a!) y, Tensor x, Tensor w, Tensor? residual, int waves, "
         "bool preshuffled=False, Tensor? w_scale=None, int ksplit=1, "
-        "Tensor? w_block_scale=None) -> ()");
+        "Tensor? w_block_scale=None, bool wide_w4=False) -> ()");
   m.def("prefill_gemm(Tensor(a!) c, Tensor a, Tensor w, Tensor? residual, int mode, Tensor? xs=None, Tensor? ws=None, int schedule=-1, int bm=0) -> ()");
   m.def("prefill_gemm_auto_bm(int m) -> int", &prefill_gemm_auto_bm);
   m.def("prefill_gemm_error() -> int", &prefill_gemm_error);
@@ -1257,6 +1292,7 @@ TORCH_LIBRARY_IMPL(atta, CUDA, m) {
   m.impl("prefill_gemm", &prefill_gemm);
   m.impl("fused_qkv_rope", &fused_qkv_rope);
   m.impl("fused_gate_up_silu", &fused_gate_up_silu);
+  m.impl("expand_mxfp4", &expand_mxfp4);
   m.impl("fused_lm_head_sample", &fused_lm_head_sample);
   m.impl("fused_lm_head_sample_lp", &fused_lm_head_sample_lp);
   m.impl("sample_finalize", &sample_finalize);

@@ -317,13 +317,21 @@ void atta_get_wide_min_rows(int* m, int* m_silu) {
 //   any                   the push variant  > 32               None    the GEMV alone pushes)
 //   MXFP4 (pre-shuffled)  any but SAMPLE    1 - 32             Skinny (its W4 build,
 //   MXFP4                 any but SAMPLE    > 32               None    gemv_w4.hip)
+//   MXFP4, wide_w4 chosen any but SAMPLE    33 - 128           Wide   (its W4 builds,
+//   MXFP4, wide_w4 chosen any but SAMPLE    > 128              None    wide_w4_mt<N>.hip)
 //   MXFP4                 SAMPLE, the push  any                None
+// wide_w4: the caller's explicit per-call choice (kWideW4 in the dtype code); a default MXFP4
+// call past 32 rows keeps having no kernel.
 // SAMPLE_LP (the sampler with the logprob record) routes as SAMPLE does, except that it has no
 // fp8 build at any row count: None.
 enum class Route { None, Skinny, Wide, MidM };
-static Route route(int M, bool ps, bool w8, bool w4, int epi) {
+static Route route(int M, bool ps, bool w8, bool w4, int epi, bool wide_w4 = false) {
   if (M < 1) return Route::None;
-  if (w4) return M <= kSkinnyMaxM && !epi_samples(epi) ? Route::Skinny : Route::None;
+  if (w4) {
+    if (epi_samples(epi)) return Route::None;
+    if (M <= kSkinnyMaxM) return Route::Skinny;
+    return wide_w4 && M <= kWideMaxM ? Route::Wide : Route::None;
+  }
   if (epi == EPI_SAMPLE_LP && w8) return Route::None;
   if (!ps) return M <= kSkinnyMaxM ? Route::Skinny : Route::None;
   const int wide_min = epi == EPI_SILU ? g_wide_min_m_silu : g_wide_min_m;
@@ -433,7 +441,9 @@ template <int EPI>
 static int launch_routed(SkinnyParams& p, int tiles, int waves, int ksplit, int dtype,
                          hipStream_t stream) {
   if (p.bscale != nullptr && p.wscale != nullptr) return -1;
-  switch (route(p.M, p.ps != 0, p.wscale != nullptr, p.bscale != nullptr, EPI)) {
+  const bool wide_w4 = (dtype & kWideW4) != 0;
+  dtype &= ~kWideW4;
+  switch (route(p.M, p.ps != 0, p.wscale != nullptr, p.bscale != nullptr, EPI, wide_w4)) {
     case Route::Skinny:
       if (p.bscale != nullptr) return launch_w4(p, EPI, tiles, waves, ksplit, dtype, stream);
       return launch_skinny<EPI>(p, tiles, waves, ksplit, dtype, stream);

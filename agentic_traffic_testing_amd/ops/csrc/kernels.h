@@ -7,6 +7,10 @@
 // OR-ed into the dtype code of the skinny GEMV entry points: weights are pre-shuffled
 // into the MFMA lane order (ops.preshuffle).
 constexpr int kPreshuffled = 256;
+// OR-ed into the dtype code by a caller that chooses the wide kernel's MXFP4 (W4) builds for
+// 33 - 128 rows over the 4-bit copies (ops.linear(..., wide_w4=True)); without it such a
+// call has no kernel (gemv.hip route()).
+constexpr int kWideW4 = 512;
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -102,6 +106,12 @@ int atta_fused_gate_up_silu(void* out, const void* x, const void* w, int M, int 
                             int64_t x_stride, int64_t out_stride, float eps, int waves,
                             int ksplit, const float* wscale, const uint8_t* bscale, int dtype,
                             hipStream_t stream);
+
+// MXFP4 codes / block scales in the layout of ops.preshuffle_mxfp4 (N weight rows, K columns)
+// -> row-major [N, K] 16-bit values at out (row stride out_stride elements), the tile row map
+// undone (rowmap 0 plain, 1 qkv, 2 silu).  expand_w4.hip.
+int atta_expand_mxfp4(void* out, const void* codes, const uint8_t* bscale, int N, int K,
+                      int64_t out_stride, int rowmap, int dtype, hipStream_t stream);
 
 // Split-K workspace of `device` for the skinny GEMVs (fp32 slots + per-tile counters, zeroed).
 int atta_set_splitk_ws(int device, float* ws, int* counters, int64_t ws_floats, int n_counters);

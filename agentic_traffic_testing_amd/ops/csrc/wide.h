@@ -36,6 +36,7 @@
 #include "common.h"
 #include "kernels.h"
 #include "skinny.h"
+#include "skinny_w4.h"
 
 namespace atta {
 namespace wide {
@@ -264,7 +265,12 @@ __device__ __forceinline__ void epi_apply(const SkinnyParams& p, const int tile,
 // 16-byte loads per tile per chunk instead of four, converted to 16-bit MFMA operands in
 // registers (v_cvt_scalef32_pk_*_fp8) and the per-row dequant scale applied to the finished
 // accumulators: weight-only quantisation, the activations stay 16-bit (no per-token quant pass)
-template <typename T, int WAVES, int MT, int EPI, bool NORM, int TPW, bool W8 = false>
+// W4: MXFP4 weights in the layout of ops.preshuffle_mxfp4 (skinny_w4.h) - a tile's 128-wide K
+// chunk is ONE 1 KiB wave load of codes (p.w) plus one dword of four e8m0 block scales per
+// lane (p.bscale: 64 B per tile and chunk, lane col's dword, byte s = K step s) - converted
+// with fp4x8_to_frag, the block scale applied by the convert: no scale after the K loop
+template <typename T, int WAVES, int MT, int EPI, bool NORM, int TPW, bool W8 = false,
+          bool W4 = false>
 __global__ __launch_bounds__(WAVES * 64) void wide_kernel(SkinnyParams p, int ntiles) {
   using MF = MfmaK32<T>;
   using frag8 = typename MF::frag8;
@@ -297,19 +303,30 @@ __global__ __launch_bounds__(WAVES * 64) void wide_kernel(SkinnyParams p, int nt
   constexpr bool norm = NORM;  // p.eps > 0: fused RMSNorm (compile-time: no branches in the loop)
   // weight register stages (chunks of weights in flight + 1): 4 x one tile, 3 x two tiles
   constexpr int kWStages = TPW == 1 ? kDeepW : 3;
-  constexpr int NW = W8 ? 2 : 4;  // 16-B weight loads per tile per chunk
-  constexpr int NWF = TPW * NW;   // weight registers (u32x4) per chunk per wave
+  static_assert(!(W8 && W4), "one weight format");
+  constexpr int NW = W4 ? 1 : W8 ? 2 : 4;  // 16-B weight loads per tile per chunk
+  // weight registers (u32x4) per chunk per wave (W4: per tile the codes, then a register whose
+  // component 0 is the chunk's block-scale dword)
+  constexpr int NWF = TPW * (W4 ? 2 : NW);
 
   // this wave's weight tiles (idle tiles of the last column block stream tile 0 and store
   // nothing: every wave takes part in the barriers)
-  // (byte pointers: a tile's pre-shuffled weights are K / 32 (16-bit) or K / 64 (fp8) 1 KiB
-  // blocks, chunk c's are blocks c * NW .. c * NW + NW - 1)
+  // (byte pointers: a tile's pre-shuffled weights are K / 32 (16-bit), K / 64 (fp8) or K / 128
+  // (MXFP4) 1 KiB blocks, chunk c's are blocks c * NW .. c * NW + NW - 1)
   const unsigned char* wp[TPW];
 #pragma unroll
   for (int j = 0; j < TPW; ++j)
     wp[j] = reinterpret_cast<const unsigned char*>(p.w) +
-            static_cast<int64_t>(tile0 + j < ntiles ? tile0 + j : 0) * (p.K / (W8 ? 64 : 32)) * 1024 +
+            static_cast<int64_t>(tile0 + j < ntiles ? tile0 + j : 0) *
+                (p.K / (W4 ? 128 : W8 ? 64 : 32)) * 1024 +
             lane * 16;
+  const unsigned char* sp[TPW];  // W4: this lane's scale dword of chunk 0
+  if constexpr (W4) {
+#pragma unroll
+    for (int j = 0; j < TPW; ++j)
+      sp[j] = p.bscale + static_cast<int64_t>(tile0 + j < ntiles ? tile0 + j : 0) * nch * 64 +
+              col * 4;
+  }
   // x pieces of this thread: piece q = tid + i * NTHR -> staged row q / 16, slot q % 16
   int xsrc[PPT];  // element offsets from p.x (32-bit: x is < 4 MB here)
   int xdst[PPT];
@@ -341,12 +358,20 @@ __global__ __launch_bounds__(WAVES * 64) void wide_kernel(SkinnyParams p, int nt
   // chunk earlier (one chunk ahead exposed the whole load latency at each chunk: 2.2 TB/s)
   u32x4 w0[NWF], w1[NWF], w2[NWF], w3[NWF], xa[PPT], xb[PPT];
   auto load_w = [&](u32x4 (&f)[NWF], int c) {
+    if constexpr (W4) {
 #pragma unroll
-    for (int j = 0; j < TPW; ++j)
+      for (int j = 0; j < TPW; ++j) {
+        f[j * 2] = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wp[j] + c * 1024));
+        f[j * 2 + 1] = u32x4{*reinterpret_cast<const uint32_t*>(sp[j] + c * 64), 0u, 0u, 0u};
+      }
+    } else {
 #pragma unroll
-      for (int s = 0; s < NW; ++s)
-        f[j * NW + s] =
-            __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(wp[j] + (c * NW + s) * 1024));
+      for (int j = 0; j < TPW; ++j)
+#pragma unroll
+        for (int s = 0; s < NW; ++s)
+          f[j * NW + s] = __builtin_nontemporal_load(
+              reinterpret_cast<const u32x4*>(wp[j] + (c * NW + s) * 1024));
+    }
   };
   auto load_x = [&](u32x4 (&xr)[PPT], int c) {
 #pragma unroll
@@ -375,13 +400,16 @@ __global__ __launch_bounds__(WAVES * 64) void wide_kernel(SkinnyParams p, int nt
   // read with its MFMA behind an lgkmcnt wait, and the wave idles on LDS latency)
   auto compute = [&](const u32x4 (&f)[NWF], int buf) {
     const unsigned char* b = lds + buf * XBUF + col * kRowB;
-    // weight fragment of tile j, K step s (fp8: converted up front, outside the MFMA groups)
+    // weight fragment of tile j, K step s (fp8 / MXFP4: converted up front, outside the MFMA
+    // groups)
     frag8 wf[TPW][4];
 #pragma unroll
     for (int j = 0; j < TPW; ++j)
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
-        if constexpr (W8) {
+        if constexpr (W4) {
+          wf[j][s] = fp4x8_to_frag<T>(f[j * 2][s], (f[j * 2 + 1][0] >> (8 * s)) & 0xffu);
+        } else if constexpr (W8) {
           const u32x4 r = f[j * 2 + (s >> 1)];
           wf[j][s] = (s & 1) ? fp8x8_to_frag<T>(r[2], r[3]) : fp8x8_to_frag<T>(r[0], r[1]);
         } else {
@@ -639,6 +667,68 @@ inline int launch_epi_w8_plain(int epi, dim3 grid, hipStream_t st, const SkinnyP
     default: return -1;
   }
 }
+
+// MXFP4 (W4) builds: 3 - 8 row blocks (33 - 128 rows; fewer rows stay on the 4-bit GEMV),
+// every wave count of the plan, one tile per wave, the W8 launcher's four epilogues.  The
+// weight stages are a quarter of the 16-bit build's registers, so the RMSNorm fold fits
+// where norm_fits says it does not in 16 bits - except at 6 waves x 8 row blocks (6 x pieces
+// per thread: 32 / 36 B of scratch per lane, hipcc kernel-resource-usage), which is not built:
+// the plan skips it.  Every other build: 0 scratch.
+constexpr bool w4_built(int mt) { return mt >= 3 && mt <= 8; }
+constexpr bool w4_norm_fits(int waves, int mt) { return !(mt == 8 && waves == 6); }
+
+template <typename T, int WAVES, int MT>
+inline int launch_epi_w4(int epi, dim3 grid, hipStream_t st, const SkinnyParams& p, int ntiles) {
+  const dim3 blk(WAVES * 64);
+  const bool norm = p.eps > 0.f;
+  switch (epi) {
+    case EPI_PLAIN:
+      if (norm) return -1;
+      wide_kernel<T, WAVES, MT, EPI_PLAIN, false, 1, false, true><<<grid, blk, 0, st>>>(p, ntiles);
+      return 0;
+    case EPI_RESADD:
+      if (norm) return -1;
+      wide_kernel<T, WAVES, MT, EPI_RESADD, false, 1, false, true><<<grid, blk, 0, st>>>(p, ntiles);
+      return 0;
+    case EPI_QKVROPE:
+      if (!norm) return -1;
+      if constexpr (w4_norm_fits(WAVES, MT)) {
+        wide_kernel<T, WAVES, MT, EPI_QKVROPE, true, 1, false, true><<<grid, blk, 0, st>>>(p, ntiles);
+        return 0;
+      }
+      return -1;
+    case EPI_SILU:
+      if (!norm) return -1;
+      if constexpr (w4_norm_fits(WAVES, MT)) {
+        wide_kernel<T, WAVES, MT, EPI_SILU, true, 1, false, true><<<grid, blk, 0, st>>>(p, ntiles);
+        return 0;
+      }
+      return -1;
+    default: return -1;  // the LM head stays 16-bit
+  }
+}
+
+template <typename T, int MT>
+inline int launch_w4_w(int epi, int waves, dim3 grid, hipStream_t st, const SkinnyParams& p,
+                       int ntiles) {
+  switch (waves) {
+    case 4: return launch_epi_w4<T, 4, MT>(epi, grid, st, p, ntiles);
+    case 6: return launch_epi_w4<T, 6, MT>(epi, grid, st, p, ntiles);
+    case 7: return launch_epi_w4<T, 7, MT>(epi, grid, st, p, ntiles);
+    case 8: return launch_epi_w4<T, 8, MT>(epi, grid, st, p, ntiles);
+    default: return -1;
+  }
+}
+
+// per-row-block translation units of the W4 builds (wide_w4_mt<N>.hip)
+int launch_w4_mt_tu(int mt, int epi, int waves, dim3 grid, hipStream_t st, const SkinnyParams& p,
+                    int ntiles, int dtype);
+#define ATTA_WIDE_W4_MT_TU(N)                                                                  \
+  int launch_w4_mt_##N(int epi, int waves, dim3 grid, hipStream_t st, const SkinnyParams& p,   \
+                       int ntiles, int dtype) {                                                \
+    return dtype == 0 ? launch_w4_w<__bf16, N>(epi, waves, grid, st, p, ntiles)                \
+                      : launch_w4_w<_Float16, N>(epi, waves, grid, st, p, ntiles);             \
+  }
 
 template <typename T, int WAVES, int MT, int TPW>
 inline int launch_epi(int epi, dim3 grid, hipStream_t st, const SkinnyParams& p, int ntiles) {

@@ -139,6 +139,30 @@ int launch_mt_tu(int mt, int epi, int waves, int tpw, dim3 grid, hipStream_t st,
   }
 }
 
+#define ATTA_WIDE_W4_MT_DECL(N)                                                               \
+  int launch_w4_mt_##N(int epi, int waves, dim3 grid, hipStream_t st, const SkinnyParams& p,   \
+                       int ntiles, int dtype);
+ATTA_WIDE_W4_MT_DECL(3)
+ATTA_WIDE_W4_MT_DECL(4)
+ATTA_WIDE_W4_MT_DECL(5)
+ATTA_WIDE_W4_MT_DECL(6)
+ATTA_WIDE_W4_MT_DECL(7)
+ATTA_WIDE_W4_MT_DECL(8)
+
+// the MXFP4 (W4) builds: 3 - 8 row blocks (wide.h w4_built)
+int launch_w4_mt_tu(int mt, int epi, int waves, dim3 grid, hipStream_t st, const SkinnyParams& p,
+                    int ntiles, int dtype) {
+  switch (mt) {
+    case 3: return launch_w4_mt_3(epi, waves, grid, st, p, ntiles, dtype);
+    case 4: return launch_w4_mt_4(epi, waves, grid, st, p, ntiles, dtype);
+    case 5: return launch_w4_mt_5(epi, waves, grid, st, p, ntiles, dtype);
+    case 6: return launch_w4_mt_6(epi, waves, grid, st, p, ntiles, dtype);
+    case 7: return launch_w4_mt_7(epi, waves, grid, st, p, ntiles, dtype);
+    case 8: return launch_w4_mt_8(epi, waves, grid, st, p, ntiles, dtype);
+    default: return -1;
+  }
+}
+
 // Grid plan: per candidate (waves, tiles per wave) - T = waves x tpw tiles per workgroup - and
 // K split S <= 8, a time estimate - rounds of the grid over the CUs x (a workgroup's weight
 // bytes + x bytes / 6 at a per-CU streaming rate, plus ~1.5 us of ramp), plus for a split the
@@ -148,7 +172,9 @@ static double env_or(const char* name, double dflt) {
   return v != nullptr ? std::atof(v) : dflt;
 }
 
-static void plan(int ntiles, int K, int M, bool norm, bool w8, int& waves, int& tpw,
+// w4 (MXFP4): the plan of the same shape in 16 bits - its cost terms are not refitted to the
+// 4-bit stream (nothing measured yet) - except that the norm fold has its own build list.
+static void plan(int ntiles, int K, int M, bool norm, bool w8, bool w4, int& waves, int& tpw,
                  int& ksplit) {
   constexpr double kCUs = 256.0, kBpus = 24e3;  // bytes per us per CU
   // cost-model knobs (env overrides for A/B runs; read once)
@@ -172,11 +198,13 @@ static void plan(int ntiles, int K, int M, bool norm, bool w8, int& waves, int& 
     for (int wi = 0; wi < 4; ++wi) {
       const int w = ws[wi];
       if (!w8 && w == kSkipW) continue;
-      if (norm && !norm_fits(w, (M + 15) / 16, tp)) continue;  // see launch_epi
+      if (norm && !(w4 ? w4_norm_fits(w, (M + 15) / 16) : norm_fits(w, (M + 15) / 16, tp)))
+        continue;  // see launch_epi / launch_epi_w4
       if (tp == 2 && !tpw2_built(w)) continue;
       const int tb = w * tp;
       const int ncb = (ntiles + tb - 1) / tb;
-      for (int s = 1; s <= 8 && nch / s >= 2; ++s) {
+      // (w4: a one-chunk K still has its unsplit plan)
+      for (int s = 1; s <= 8 && (nch / s >= 2 || (w4 && s == 1)); ++s) {
         const double rounds = std::ceil(ncb * s / kCUs);
         const double kslice = static_cast<double>(K) / s;
         const double bytes = tb * 16.0 * kslice * (w8 ? 1.0 : 2.0) + mpad * kslice * 2.0 / kXDiv;
@@ -204,7 +232,8 @@ static void plan(int ntiles, int K, int M, bool norm, bool w8, int& waves, int& 
 using namespace atta;
 
 // Launch the wide kernel for a SkinnyParams already filled by a gemv.hip entry point (x, w
-// pre-shuffled 16-bit, y / epilogue fields, eps, M, N, K).  ntiles: 16-column tiles (N / 16;
+// pre-shuffled 16-bit / fp8 with wscale / MXFP4 codes with bscale, y / epilogue fields, eps,
+// M, N, K).  ntiles: 16-column tiles (N / 16;
 // SiLU: inter / 8).  waves / ksplit 0 = planned here.  Returns 0, -1 (unsupported shape) or
 // -2 (split-K workspace missing / too small).
 // split-K slab precision of the wide kernel (atta_set_splitk_half): 0 fp32, 1 bf16
@@ -216,6 +245,8 @@ int atta_wide_launch(SkinnyParams& p, int epi, int ntiles, int waves, int ksplit
                      hipStream_t stream) {
   if (p.M < 1 || p.M > kWideMaxM || p.K % wide::kKC != 0 || !p.ps) return -1;
   const bool w8 = p.wscale != nullptr;  // fp8 weights (the W8 builds)
+  const bool w4 = p.bscale != nullptr;  // MXFP4 weights (the W4 builds)
+  if (w4 && (w8 || !wide::w4_built((p.M + 15) / 16))) return -1;
   // waves 14 / 16 / 17 / 18 in an explicit plan = 4 / 6 / 7 / 8 waves x two tiles per wave
   // (measured slower and not built: such a plan returns -1 from the launcher)
   int tpw = 1;
@@ -224,7 +255,7 @@ int atta_wide_launch(SkinnyParams& p, int epi, int ntiles, int waves, int ksplit
     waves -= 10;
   }
   if (waves <= 0 || ksplit <= 0)
-    wide::plan(ntiles, p.K, p.M, p.eps > 0.f, w8, waves, tpw, ksplit);
+    wide::plan(ntiles, p.K, p.M, p.eps > 0.f, w8, w4, waves, tpw, ksplit);
   if (waves != 4 && waves != 6 && waves != 7 && waves != 8) return -1;
   if (ksplit < 1 || p.K / wide::kKC < ksplit) return -1;
   // 16-row blocks: rows padded to the next 16 only (75 rows: 80, not 96)
@@ -247,7 +278,9 @@ int atta_wide_launch(SkinnyParams& p, int epi, int ntiles, int waves, int ksplit
   (void)n_counters;
   p.ksplit = ksplit;
   const dim3 grid(ncb, ksplit);
-  int rc = wide::launch_mt_tu(mt, epi, waves, tpw, grid, stream, p, ntiles, dtype);
+  int rc = w4 ? (tpw == 1 ? wide::launch_w4_mt_tu(mt, epi, waves, grid, stream, p, ntiles, dtype)
+                          : -1)
+              : wide::launch_mt_tu(mt, epi, waves, tpw, grid, stream, p, ntiles, dtype);
   if (rc) return rc;
   if (ksplit > 1) {
     p.wg_trace = nullptr;

@@ -479,6 +479,8 @@ def build_config(args):
         kw["device"] = args.device
     if getattr(args, "quantization", None):
         kw["quantization"] = args.quantization
+    if getattr(args, "mxfp4_weights_only", False):
+        kw["mxfp4_weights_only"] = True
     if getattr(args, "burst_window_ms", None) is not None:
         kw["burst_window_ms"] = args.burst_window_ms
     if getattr(args, "burst_gap_ms", None) is not None:
@@ -563,6 +565,9 @@ def make_parser() -> argparse.ArgumentParser:
                    default=os.environ.get("LLM_QUANTIZATION", "").lower() or None,
                    help="weight-only quantisation: fp8 (OCP e4m3fn, per-row scales) or mxfp4 "
                         "(OCP Microscaling FP4; steps of <= 32 rows stream 4-bit weights)")
+    p.add_argument("--mxfp4-weights-only", action="store_true",
+                   help="with --quantization mxfp4: keep the layer projections in 4 bits only "
+                        "(no 16-bit copies; steps past 128 rows expand into a shared scratch)")
     p.add_argument("--data-parallel-size", "--dp-size", type=int, default=1,
                    help="engine replicas, one per GPU, behind a router on --port "
                         "(parallel/dp_router.py)")
