@@ -271,6 +271,13 @@ class EngineConfig:
     # (about 2.5 B of extra traffic per weight and step: why this is opt-in).  GPU only.
     # --mxfp4-weights-only / LLM_MXFP4_WEIGHTS_ONLY
     mxfp4_weights_only: bool = False
+    # quantization="mxfp4" only (W4A8): steps that no fused 4-bit kernel takes (more than 128
+    # rows) quantise their activations per token to e4m3, as under "fp8", and multiply them by
+    # the resident 4-bit weights on the block-scaled MFMA (ops.gemm_w4a8) - prefill reads 4.25
+    # bits per weight; with mxfp4_weights_only there is then no expand pass and no scratch.
+    # Opt-in: the numerics of such steps change.  Either memory mode.
+    # --mxfp4-fp8-activations / LLM_MXFP4_FP8_ACTIVATIONS
+    mxfp4_fp8_activations: bool = False
     num_kv_blocks: int = 0               # 0 = size from gpu_memory_utilization
     load_format: str = "auto"            # auto | dummy (random init) | safetensors
     # tensor parallelism: "auto" = RCCL ("nccl") on GPUs, gloo on CPU; "gloo" forces the
@@ -305,6 +312,9 @@ class EngineConfig:
                              f"= {self.tensor_parallel_size} is not supported with it")
         if self.mxfp4_weights_only and self.quantization != "mxfp4":
             raise ValueError("mxfp4_weights_only needs quantization='mxfp4' "
+                             f"(quantization={self.quantization!r})")
+        if self.mxfp4_fp8_activations and self.quantization != "mxfp4":
+            raise ValueError("mxfp4_fp8_activations needs quantization='mxfp4' "
                              f"(quantization={self.quantization!r})")
         if self.speculative not in ("", "ngram"):
             raise ValueError(f"speculative={self.speculative!r}: '' or 'ngram'")
@@ -358,6 +368,9 @@ class EngineConfig:
             kw["quantization"] = env["LLM_QUANTIZATION"].strip().lower()
         if env.get("LLM_MXFP4_WEIGHTS_ONLY"):
             kw["mxfp4_weights_only"] = env["LLM_MXFP4_WEIGHTS_ONLY"].strip().lower() in (
+                "1", "true", "yes", "on")
+        if env.get("LLM_MXFP4_FP8_ACTIVATIONS"):
+            kw["mxfp4_fp8_activations"] = env["LLM_MXFP4_FP8_ACTIVATIONS"].strip().lower() in (
                 "1", "true", "yes", "on")
         kw.update({k: v for k, v in overrides.items() if v is not None})
         return cfg.replace(**kw)

@@ -147,7 +147,8 @@ class ModelRunner:
         t0 = time.perf_counter()
         self.model = LlamaModel(model_cfg, self.dtype, self.device, tp_rank, tp_size, comm,
                                 quantization=cfg.quantization,
-                                mxfp4_weights_only=cfg.mxfp4_weights_only)
+                                mxfp4_weights_only=cfg.mxfp4_weights_only,
+                                mxfp4_fp8_activations=cfg.mxfp4_fp8_activations)
         self.model.prefill_gemm = cfg.prefill_gemm
         self.model.prefill_gemm_min_rows = cfg.prefill_gemm_min_rows
         self.model.small_prefill_fused = cfg.small_prefill_fused
@@ -179,14 +180,21 @@ class ModelRunner:
                   f"{rw['codes4'] / 2**30:.2f} GiB, block scales {rw['scales4'] / 2**30:.2f} GiB, "
                   f"16-bit rest {rw['w16'] / 2**30:.2f} GiB, expand scratch "
                   f"{rw['scratch'] / 2**30:.2f} GiB", flush=True)
+        if cfg.mxfp4_fp8_activations:
+            print("[atta] mxfp4 fp8 activations (W4A8): steps without a fused 4-bit kernel run "
+                  "e4m3 activations x 4-bit weights (ops.gemm_w4a8)"
+                  + (", no expand scratch" if cfg.mxfp4_weights_only else ""), flush=True)
         if self.is_cuda:
             # split-K GEMV workspace up front (32 MiB): a split chosen while a decode graph is
             # being captured (ATTA_DECODE_KSPLIT, TP shards) must not allocate inside the capture
             ops.ensure_splitk_workspace(self.device)
             if cfg.fused_decode:
-                ops.warm_wide_kernels(self.device, self.dtype, wide_w4=cfg.mxfp4_weights_only)
+                ops.warm_wide_kernels(self.device, self.dtype, wide_w4=cfg.mxfp4_weights_only,
+                                      expand=not cfg.mxfp4_fp8_activations)
             if cfg.startup_warmup:
                 self.warm_library_gemms()
+                if cfg.mxfp4_fp8_activations:
+                    self.warm_w4a8_kernels()
         self.block_size = cfg.block_size
         self.bt_width = math.ceil(cfg.max_model_len / cfg.block_size)
         self.part_tokens = cfg.decode_partition_tokens
@@ -1101,6 +1109,8 @@ class ModelRunner:
         for name in ("qkv", "o", "gate_up", "down"):
             w = getattr(L, name)
             if w is None:
+                if self.model.w4_scratch is None:
+                    continue  # with mxfp4_fp8_activations: no library GEMM reads this projection
                 # mxfp4_weights_only: the library GEMMs read the expand scratch; for loading
                 # their code objects its current contents do as well as any
                 n_, k_ = self.model.proj_shape(L, name)
@@ -1128,6 +1138,29 @@ class ModelRunner:
                 else:
                     continue
                 n += 1
+        torch.cuda.synchronize(self.device)
+        return n
+
+    def warm_w4a8_kernels(self) -> int:
+        """mxfp4_fp8_activations: run both builds of the W4A8 GEMM (plain, SiLU epilogue) once
+        on the first layer's 4-bit copies, with the quantiser modes of its chain, so their code
+        objects load at engine start.  Returns the launches."""
+        if not self.is_cuda or not self.model.layers or self.model.layers[0].qkv_w4 is None:
+            return 0
+        from ..models.llama import W4_ROWMAPS
+
+        L, n = self.model.layers[0], 0
+        with torch.inference_mode():
+            for proj, mode in (("qkv", ops.GEMM_PLAIN), ("gate_up", ops.GEMM_SILU)):
+                wq, sq = getattr(L, proj + "_w4"), getattr(L, proj + "_b4")
+                x = torch.zeros(1, wq.shape[1] * 2, dtype=torch.bfloat16, device=self.device)
+                xq, xs = ops.quant_rows_fp8(x)
+                ops.gemm_w4a8(xq, xs, wq, sq, W4_ROWMAPS[proj], mode)
+                n += 1
+            x = torch.zeros(1, self.mcfg.hidden_size, dtype=torch.bfloat16, device=self.device)
+            ops.quant_rows_fp8(x, ops.QUANT_NORM, L.input_norm, self.mcfg.rms_norm_eps)
+            ops.quant_rows_fp8(x, ops.QUANT_ADDNORM, L.input_norm, self.mcfg.rms_norm_eps,
+                               x.clone())
         torch.cuda.synchronize(self.device)
         return n
 

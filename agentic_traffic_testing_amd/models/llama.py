@@ -28,7 +28,7 @@ import torch.nn.functional as F
 from .. import ops
 from ..config import ModelConfig
 from . import step_plan as sp
-from .step_plan import FUSED, GEMM, GEMM_SPLITK
+from .step_plan import FUSED, GEMM, GEMM_SPLITK, GEMM_W4A8
 from ..ops import reference as ref
 
 DTYPES = {"bfloat16": torch.bfloat16, "bf16": torch.bfloat16, "float16": torch.float16,
@@ -37,7 +37,7 @@ DTYPES = {"bfloat16": torch.bfloat16, "bf16": torch.bfloat16, "float16": torch.f
 
 
 # tile row map of each projection's 4-bit copy (ops.preshuffle_mxfp4)
-W4_ROWMAPS = {"qkv": "qkv", "o": "plain", "gate_up": "silu", "down": "plain"}
+W4_ROWMAPS = sp.W4_ROWMAPS
 
 
 def torch_dtype(name: str) -> torch.dtype:
@@ -96,7 +96,7 @@ class LayerWeights:
 class LlamaModel:
     def __init__(self, cfg: ModelConfig, dtype=torch.bfloat16, device="cuda", tp_rank: int = 0,
                  tp_size: int = 1, tp_group=None, quantization: str = "",
-                 mxfp4_weights_only: bool = False):
+                 mxfp4_weights_only: bool = False, mxfp4_fp8_activations: bool = False):
         # tp_group: parallel.comm.TPComm (required when tp_size > 1)
         # quantization: "" (16-bit weights) | "fp8" (OCP e4m3fn weights, per-row scales; on the
         # CPU reference path the dequantised values are stored instead) | "mxfp4" (OCP
@@ -116,6 +116,19 @@ class LlamaModel:
         if mxfp4_weights_only and torch.device(device).type != "cuda":
             raise ValueError("mxfp4_weights_only needs a GPU: the CPU reference computes with "
                              "the dequantised 16-bit weights")
+        # mxfp4_fp8_activations (W4A8): a step that no fused 4-bit kernel takes runs the
+        # activation-quantised chain with every GEMM on ops.gemm_w4a8 - per-token e4m3
+        # activations times the resident 4-bit weights; with mxfp4_weights_only there is then
+        # no expand pass and no scratch.  Numerics of its own (as under "fp8": activations of
+        # such steps are rounded to e4m3); the CPU reference runs the same arithmetic on the
+        # dequantised weights.
+        if mxfp4_fp8_activations and quantization != "mxfp4":
+            raise ValueError("mxfp4_fp8_activations needs quantization 'mxfp4'")
+        if (mxfp4_fp8_activations and torch.device(device).type == "cuda"
+                and dtype != torch.bfloat16):
+            raise ValueError("mxfp4_fp8_activations needs bfloat16 activations on a GPU "
+                             "(ops.gemm_w4a8 writes bf16)")
+        self.w4a8 = bool(mxfp4_fp8_activations)
         self.w4_only = bool(mxfp4_weights_only)
         self.w4_scratch = None  # [max N * K] 16-bit, allocated once at load
         self.quant = quantization
@@ -264,8 +277,10 @@ class LlamaModel:
     def _alloc_w4_scratch(self):
         """The one 16-bit scratch of the weights-only mode: the largest projection's N * K
         values, shared by every layer and projection (a step expands into it in stream order,
-        just before the GEMM that reads it).  Allocated once at load."""
-        if self.w4_only and self.layers:
+        just before the GEMM that reads it).  Allocated once at load.  None with
+        mxfp4_fp8_activations: every step without a 4-bit fused kernel runs ops.gemm_w4a8 on
+        the 4-bit copies themselves."""
+        if self.w4_only and self.layers and not self.w4a8:
             n = max(math.prod(self.proj_shape(self.layers[0], p)) for p in sp.PROJS)
             self.w4_scratch = torch.empty(n, dtype=self.dtype, device=self.device)
 
@@ -481,7 +496,7 @@ class LlamaModel:
                     else:
                         xq, xs = ops.quant_rows_fp8(pending, ops.QUANT_ADDNORM, L.input_norm,
                                                     eps, residual)
-                    qkv = self._gemm8(plan.qkv, xq, xs, L.qkv, L.qkv_s, dt)
+                    qkv = self._chain_gemm(plan.qkv, L, "qkv", xq, xs, dt)
                 else:
                     x = ops.rms_norm(residual, L.input_norm, eps)
                     wqkv = self._w16(L, "qkv")
@@ -499,16 +514,19 @@ class LlamaModel:
                                       self.scale, out=attn)
             if plan.fp8_chain:
                 aq, as_ = ops.quant_rows_fp8(attn.view(T, nq * D))
-                y = self._all_reduce(self._gemm8(plan.o, aq, as_, L.o, L.o_s, dt))
+                y = self._all_reduce(self._chain_gemm(plan.o, L, "o", aq, as_, dt))
                 xq, xs = ops.quant_rows_fp8(y, ops.QUANT_ADDNORM, L.post_norm, eps, residual)
                 if plan.gate_up == GEMM:
                     # SiLU-mul fused into the gate_up GEMM epilogue: [T, I] out, plain quant
                     act = ops.prefill_gemm(xq, L.gate_up, ops.GEMM_SILU, xs=xs, ws=L.gate_up_s)
                     aq, as_ = ops.quant_rows_fp8(act)
+                elif plan.gate_up == GEMM_W4A8:
+                    act = self._chain_gemm(plan.gate_up, L, "gate_up", xq, xs, dt, ops.GEMM_SILU)
+                    aq, as_ = ops.quant_rows_fp8(act)
                 else:
                     gu = ops.gemm_fp8(xq, xs, L.gate_up, L.gate_up_s, dt)
                     aq, as_ = ops.quant_rows_fp8(gu, ops.QUANT_SILU)
-                pending = self._all_reduce(self._gemm8(plan.down, aq, as_, L.down, L.down_s, dt))
+                pending = self._all_reduce(self._chain_gemm(plan.down, L, "down", aq, as_, dt))
                 continue
             self._proj_residual(plan.o, attn.view(T, nq * D), L, "o", residual)
             if plan.gate_up == FUSED:
@@ -579,7 +597,7 @@ class LlamaModel:
             gemm_tuned=self.gemm_tuned, prefill_gemm=self.prefill_gemm,
             prefill_gemm_min_rows=self.prefill_gemm_min_rows,
             small_prefill_fused=self.small_prefill_fused, fused_decode=self.fused_decode,
-            w4_only=self.w4_only, midm_routes=self.MIDM_ROUTES, pg_auto=self._PG_AUTO,
+            w4_only=self.w4_only, w4a8=self.w4a8, midm_routes=self.MIDM_ROUTES, pg_auto=self._PG_AUTO,
             pg_auto_untuned=self._PG_AUTO_UNTUNED, pg_splitk=self._PG_SPLITK,
             midm_fp8_rows=self.MIDM_FP8_ROWS, fp8_gate_up_wide_max=self.FP8_GATE_UP_WIDE_MAX,
             fp8_fused_max_rows=self.FP8_FUSED_MAX_ROWS))
@@ -591,6 +609,24 @@ class LlamaModel:
         if backend == GEMM:
             return ops.prefill_gemm(xq, w, xs=xs, ws=ws)
         return ops.gemm_fp8(xq, xs, w, ws, dt)
+
+    def _chain_gemm(self, backend, L, proj, xq, xs, dt, mode=ops.GEMM_PLAIN):
+        """One projection of the activation-quantised chain on the plan's backend: an fp8
+        weight GEMM (``_gemm8``), or the W4A8 GEMM on the layer's resident 4-bit copy.  The CPU
+        reference has no 4-bit copies: it runs the W4A8 arithmetic (e4m3 activations, fp32
+        accumulation, bf16 out) on the dequantised 16-bit weight."""
+        if backend != GEMM_W4A8:
+            return self._gemm8(backend, xq, xs, getattr(L, proj), getattr(L, proj + "_s"), dt)
+        wq = getattr(L, proj + "_w4")
+        if wq is not None:
+            return ops.gemm_w4a8(xq, xs, wq, getattr(L, proj + "_b4"), W4_ROWMAPS[proj], mode)
+        if xq.is_cuda:
+            raise RuntimeError("mxfp4_fp8_activations: no 4-bit copies (prepare_decode_weights "
+                               "not run?)")
+        y = (xq.view(torch.float8_e4m3fn).float() @ getattr(L, proj).float().t()) * xs
+        if mode == ops.GEMM_SILU:
+            y = F.silu(y[:, :self.inter]) * y[:, self.inter:]
+        return y.to(torch.bfloat16).to(dt)
 
     def _proj_residual(self, backend, x, L, proj, residual):
         """residual += x @ w.T (row-parallel o / down projection; TP: all-reduced partial

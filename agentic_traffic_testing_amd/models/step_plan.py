@@ -13,6 +13,9 @@ usable without a GPU.  Backends:
 * ``gemm_splitk``  the same with the split-K schedule (o / down)
 * ``lib``          the library GEMM (``ops.linear``, which itself sends at most 32 row-major rows
                    to the GEMV, or ``ops.gemm_fp8``) with separate norm / RoPE / SiLU kernels
+* ``gemm_w4a8``    the MXFP4 W4A8 GEMM (``ops.gemm_w4a8``): row-quantised e4m3 activations times
+                   the resident 4-bit weights on the block-scaled MFMA, inside the
+                   activation-quantised chain ([4]); gate_up multiplies SiLU in its epilogue
 
 The table, for a GPU model with the defaults (``prefill_gemm="auto"``, ``small_prefill_fused``
 and ``fused_decode`` on, every projection's K in whole wave steps, ``ATTA_WIDE_MAX_M`` 128,
@@ -38,6 +41,7 @@ and ``fused_decode`` on, every projection's K in whole wave steps, ``ATTA_WIDE_M
 | mxfp4, weights only  | 1   | 1-32               | fused | fused       | fused       | fused    |
 | mxfp4, weights only  | 1   | 33-128 [6]         | fused | fused       | fused       | fused    |
 | mxfp4, weights only  | 1   | the rest [6]       | expand + the "16-bit, the rest" row           |
+| mxfp4, w4a8 [7]      | 1   | 129 and more       | ``gemm_w4a8`` on all four                     |
 
 [1] no tuned library table loaded: ``gemm`` from 2048 rows (bf16) / 2560 rows (fp8).
 [2] no tuned library table loaded, TP = 1, bf16: ``gemm_splitk`` at 448-1152 rows.
@@ -57,13 +61,21 @@ and ``fused_decode`` on, every projection's K in whole wave steps, ``ATTA_WIDE_M
     just before its GEMM and is planned as the same model without quantisation and without
     pre-shuffled copies (library GEMMs, ``gemm`` where [1] / [2] route it, rows padded).
 
+[7] ``w4a8`` (``mxfp4_fp8_activations``, either memory mode; it goes before the two "the
+    rest" rows above): a step of more than 128 rows - and a smaller one that would otherwise
+    expand, or run padded library GEMMs because the fused path is off - runs the chain of [4]
+    with every GEMM on ``ops.gemm_w4a8``: no expand pass, no 16-bit scratch, rows not padded.
+    The CPU reference gets the same plan and runs the chain's arithmetic on the dequantised
+    weights.
+
 fp8 weights are always pre-shuffled on a GPU (without the copies no fp8 step runs fused).  With
 the fused path off (either switch, a K that is not whole wave steps, the kernel limits) a step
 takes "the rest" rows; 16-bit weights other than bf16 never take ``gemm``.
 ``prefill_gemm="hipblaslt"`` drops [1] and [2]; ``"atta"`` turns every ``lib`` above into
 ``gemm`` from ``prefill_gemm_min_rows`` rows where the GEMM takes the shape
 (``ops.prefill_gemm_shape_ok``).  Rows are padded to the tuned library buckets by the runner
-(``pad_rows``) unless a step of <= 128 rows runs fused.  On the CPU everything is ``lib``.
+(``pad_rows``) unless a step of <= 128 rows runs fused.  On the CPU everything is ``lib``
+(but [7]).
 """
 from __future__ import annotations
 
@@ -75,7 +87,10 @@ import torch
 from .. import ops
 
 PROJS = ("qkv", "o", "gate_up", "down")
+# tile row map of each projection's 4-bit copy (ops.preshuffle_mxfp4)
+W4_ROWMAPS = {"qkv": "qkv", "o": "plain", "gate_up": "silu", "down": "plain"}
 FUSED, GEMM, GEMM_SPLITK, LIB = "fused", "gemm", "gemm_splitk", "lib"
+GEMM_W4A8 = "gemm_w4a8"
 
 # "auto" routing of the prefill projections: (weight dtype, projection) -> the smallest row count
 # from which the hand-written GEMM beat hipBLASLt in the cold-weight A/B on the 8B shapes.
@@ -151,6 +166,8 @@ class StepFacts:
     small_prefill_fused: bool = True
     fused_decode: bool = True
     w4_only: bool = False       # mxfp4_weights_only: no 16-bit projections exist
+    w4a8: bool = False          # mxfp4_fp8_activations: steps past the 4-bit fused kernels run
+                                # the activation-quantised chain on ops.gemm_w4a8
     # the measured tables above
     midm_routes: dict = field(default_factory=lambda: MIDM_ROUTES)
     pg_auto: dict = field(default_factory=lambda: PG_AUTO)
@@ -227,6 +244,20 @@ def step_plan(T: int, f: StepFacts) -> StepPlan:
         if (f.gpu and f.tp_size == 1 and f.small_prefill_fused and f.fused_decode and f.dims_ok
                 and ops.fused_kernel(T, True, mxfp4=True, wide_w4=f.w4_only) is not None):
             return StepPlan(FUSED, FUSED, FUSED, FUSED, fp8_chain=False, pad_rows=False)
+        # w4a8: past the wide kernel's rows, and wherever the step would otherwise expand
+        # (weights only) or leave the small fused step of the 16-bit copies for padded library
+        # GEMMs; the CPU reference follows the row rule alone, as a GPU with the defaults does
+        if f.w4a8 and (f.w4_only or T > ops.WIDE_ROWS
+                       or (f.gpu and step_plan(T, replace(f, quant="")).pad_rows)):
+            # every shape the resident layout admits (K % 128, 16-row tiles in pairs) is one the
+            # GEMM takes; a GPU model whose shapes it does not take cannot run this mode at all
+            if f.gpu and not all(
+                    ops.gemm_w4a8_shape_ok(*f.kn(p), ops.GEMM_SILU if p == "gate_up"
+                                           else ops.GEMM_PLAIN, W4_ROWMAPS[p]) for p in PROJS):
+                raise ValueError("mxfp4_fp8_activations: a projection shape ops.gemm_w4a8 does "
+                                 "not take (K % 128 == 0, N % 32 == 0)")
+            return StepPlan(GEMM_W4A8, GEMM_W4A8, GEMM_W4A8, GEMM_W4A8, fp8_chain=True,
+                            pad_rows=False)
         if f.w4_only:
             # expand + the plan of the unquantised model without pre-shuffled copies, library
             # side only: a row-major GEMV would re-read the scratch it was just expanded into

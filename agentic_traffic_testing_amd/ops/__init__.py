@@ -596,7 +596,8 @@ def midm_plan(m: int, ntiles: int, k: int, epi: int) -> tuple[int, int]:
 MIDM_BUILT = (3, 4, 5, 6, 8, 10, 12)  # row-block heights / 16 (csrc/midm_b<N>.hip)
 
 
-def warm_wide_kernels(device, dtype=torch.bfloat16, wide_w4: bool = False) -> None:
+def warm_wide_kernels(device, dtype=torch.bfloat16, wide_w4: bool = False,
+                      expand: bool = True) -> None:
     """Launch one tiny GEMM from every translation unit of the wide (wide_mt<N>.hip: one per
     16-row block count the limits allow) and mid-M kernels (midm_b<N>.hip per row-block
     height, midm.hip's split-K reduce), so every code object is loaded at engine start: HIP
@@ -605,7 +606,8 @@ def warm_wide_kernels(device, dtype=torch.bfloat16, wide_w4: bool = False) -> No
     ms the first time a 50 / 95-row burst ran, scripts/gpu/probe_fanout_ttft.py).  Only
     kernels the configured limits can route to are launched, and the caller's wide row
     thresholds are restored afterwards.  ``wide_w4`` (the weights-only MXFP4 mode): the wide
-    kernel's 4-bit translation units (wide_w4_mt<N>.hip) and the expand kernel as well."""
+    kernel's 4-bit translation units (wide_w4_mt<N>.hip) and - unless ``expand`` is off: with
+    mxfp4_fp8_activations no step expands - the expand kernel as well."""
     dev = torch.device(device)
     top = fused_max_rows()
     if dev.type != "cuda" or top <= SKINNY_MAX_M:
@@ -630,7 +632,8 @@ def warm_wide_kernels(device, dtype=torch.bfloat16, wide_w4: bool = False) -> No
             for rows in range(SKINNY_ROWS + 16, fused_max_rows(mxfp4=True, wide_w4=True) + 1, 16):
                 linear(torch.zeros(rows, 256, dtype=dtype, device=dev), wq, w_block_scale=sq,
                        wide_w4=True)
-            expand_mxfp4(wq, sq, "plain", torch.empty(128, 256, dtype=dtype, device=dev))
+            if expand:
+                expand_mxfp4(wq, sq, "plain", torch.empty(128, 256, dtype=dtype, device=dev))
     finally:
         set_wide_min_rows(*prev)
     torch.cuda.synchronize(dev)
@@ -900,6 +903,59 @@ def prefill_gemm(x: torch.Tensor, w: torch.Tensor, mode: int = GEMM_PLAIN,
         out = torch.empty(x.shape[0], n, dtype=torch.bfloat16, device=x.device)
     _native().prefill_gemm(out, x, w, None, mode, xs_, ws_, sched, bm)
     return out
+
+
+def gemm_w4a8_shape_ok(k: int, n: int, mode: int = GEMM_PLAIN, rowmap: str | None = None) -> bool:
+    """The shape rule of ``gemm_w4a8`` for a weight of ``n`` rows and ``k`` columns, without the
+    tensors: K in whole 128-wide chunks of the resident layout, N in whole 32-row MFMA
+    fragments (the "qkv" rowmap: whole 128-dim heads); the SiLU mode is the "silu" rowmap's."""
+    if mode not in (GEMM_PLAIN, GEMM_SILU) or (mode == GEMM_SILU and rowmap not in (None, "silu")):
+        return False
+    return k >= 128 and k % 128 == 0 and n >= 32 and n % (128 if rowmap == "qkv" else 32) == 0
+
+
+def gemm_w4a8(xq: torch.Tensor, xs: torch.Tensor, wq: torch.Tensor, sq: torch.Tensor,
+              rowmap: str, mode: int = GEMM_PLAIN, out: torch.Tensor | None = None
+              ) -> torch.Tensor:
+    """MXFP4 W4A8 GEMM: ``y[m, n] = xs[m] * sum_k e4m3(xq[m, k]) * w[n, k]`` with ``w`` the
+    values of one projection's 4-bit copy (``wq`` / ``sq`` exactly as ``preshuffle_mxfp4(codes,
+    scales, rowmap)`` returns them), fp32 accumulation, one rounding to bf16.  ``xq`` uint8
+    [M, K] e4m3fn with fp32 row scales ``xs`` [M] or [M, 1] (``quant_rows_fp8``).
+    ``GEMM_PLAIN``: [M, N] in the ORIGINAL weight-row order (the row map undone);
+    ``GEMM_SILU`` ("silu" rowmap): ``silu(gate) * up`` -> [M, N / 2].  GPU tensors run the
+    block-scaled MFMA kernel
+    (csrc/prefill_gemm_w4a8.hip); CPU tensors compute the same from
+    ``dequantize_mxfp4(*unshuffle_mxfp4(wq, sq, rowmap))`` in fp32.  A shape outside
+    ``gemm_w4a8_shape_ok`` raises ValueError."""
+    if rowmap not in ROWMAPS:
+        raise ValueError(f"unknown rowmap {rowmap}")
+    if xq.dim() != 2 or wq.dim() != 2 or xq.dtype != torch.uint8 or wq.dtype != torch.uint8:
+        raise ValueError("gemm_w4a8: uint8 xq [M, K] and wq [N, K / 2]")
+    n, k = wq.shape[0], wq.shape[1] * 2
+    if not gemm_w4a8_shape_ok(k, n, mode, rowmap) or xq.shape[1] != k:
+        raise ValueError(f"gemm_w4a8: K % 128 == 0, N % 32 == 0 (qkv rowmap: N % 128 == 0), the "
+                         f"SiLU mode with the silu rowmap; got x {tuple(xq.shape)}, N {n}, K {k}, "
+                         f"mode {mode}, rowmap {rowmap}")
+    if xs.numel() != xq.shape[0]:
+        raise ValueError("gemm_w4a8: one scale per row of xq")
+    width = n // 2 if mode == GEMM_SILU else n
+    if not xq.is_cuda:
+        w = dequantize_mxfp4(*unshuffle_mxfp4(wq, sq, rowmap), torch.float32)
+        y = (xq.view(torch.float8_e4m3fn).float() @ w.t()) * xs.reshape(-1, 1).float()
+        if mode == GEMM_SILU:
+            y = torch.nn.functional.silu(y[:, :width]) * y[:, width:]
+        y = y.to(torch.bfloat16)
+        if out is not None:
+            out.copy_(y)
+            return out
+        return y
+    if out is None:
+        out = torch.empty(xq.shape[0], width, dtype=torch.bfloat16, device=xq.device)
+    _native().gemm_w4a8(out, xq, xs.reshape(-1), wq, sq, ROWMAPS[rowmap], mode)
+    return out
+
+
+W4A8_TILE = 64  # activation rows per tile of csrc/prefill_gemm_w4a8.hip
 
 
 _PG_SCHEDULE = "hybrid"  # the configured (process-wide) default schedule

@@ -750,6 +750,53 @@ void expand_mxfp4(at::Tensor out, const at::Tensor& wq, const at::Tensor& sq, in
            "expand_mxfp4");
 }
 
+// y := xs * e4m3(xq) . mxfp4(wq, sq)^T (ops.gemm_w4a8): xq uint8 [M, K], xs fp32 [M], wq / sq
+// one projection's 4-bit copy (ops.preshuffle_mxfp4, tile row map `rowmap`); mode 0 plain
+// ([M, N], original row order) / 2 silu(gate) * up ([M, N / 2], rowmap 2)
+void gemm_w4a8(at::Tensor y, const at::Tensor& xq, const at::Tensor& xs, const at::Tensor& wq,
+               const at::Tensor& sq, int64_t rowmap, int64_t mode) {
+  check_dev(y, "y");
+  TORCH_CHECK(xq.is_cuda() && xs.is_cuda() && wq.is_cuda() && sq.is_cuda() &&
+                  xq.device() == y.device() && xs.device() == y.device() &&
+                  wq.device() == y.device() && sq.device() == y.device(),
+              "gemm_w4a8: one GPU");
+  TORCH_CHECK_VALUE(xq.scalar_type() == at::kByte && wq.scalar_type() == at::kByte &&
+                        sq.scalar_type() == at::kByte && xs.scalar_type() == at::kFloat &&
+                        y.scalar_type() == at::kBFloat16,
+                    "gemm_w4a8: uint8 xq / wq / sq, fp32 xs, bf16 y");
+  TORCH_CHECK_VALUE(xq.dim() == 2 && y.dim() == 2 && wq.dim() == 2 && sq.dim() == 2 &&
+                        xq.stride(1) == 1 && y.stride(1) == 1 && wq.is_contiguous() &&
+                        sq.is_contiguous() && xs.is_contiguous(),
+                    "gemm_w4a8: layout");
+  const int64_t M = xq.size(0), K = xq.size(1), N = wq.size(0);
+  TORCH_CHECK_VALUE(mode == 0 || mode == 2, "gemm_w4a8: mode 0 (plain) / 2 (silu)");
+  TORCH_CHECK_VALUE(rowmap >= 0 && rowmap <= 2 && (rowmap != 1 || N % 128 == 0) &&
+                        (mode != 2 || rowmap == 2),
+                    "gemm_w4a8: rowmap 0 (plain) / 1 (qkv: whole 128-dim heads) / 2 (silu); the "
+                    "silu mode needs the silu rowmap");
+  TORCH_CHECK_VALUE(M >= 1 && K >= 128 && K % 128 == 0 && N >= 32 && N % 32 == 0 &&
+                        wq.size(1) * 2 == K && sq.size(0) == N && sq.size(1) * 32 == K &&
+                        xs.numel() == M && M < (int64_t(1) << 31) && N < (int64_t(1) << 31) &&
+                        K < (int64_t(1) << 31),
+                    "gemm_w4a8: K % 128 == 0, N % 32 == 0, wq [N, K / 2], sq [N, K / 32], xs [M]");
+  TORCH_CHECK_VALUE(y.size(0) == M && y.size(1) == (mode == 2 ? N / 2 : N),
+                    "gemm_w4a8: y [M, N] (silu mode: [M, N / 2])");
+  TORCH_CHECK_VALUE(xq.stride(0) >= K && xq.stride(0) % 16 == 0 && y.stride(0) >= y.size(1) &&
+                        y.stride(0) % 4 == 0 &&
+                        reinterpret_cast<uintptr_t>(xq.data_ptr()) % 16 == 0 &&
+                        reinterpret_cast<uintptr_t>(y.data_ptr()) % 8 == 0 &&
+                        reinterpret_cast<uintptr_t>(wq.data_ptr()) % 16 == 0 &&
+                        reinterpret_cast<uintptr_t>(sq.data_ptr()) % 4 == 0 &&
+                        reinterpret_cast<uintptr_t>(xs.data_ptr()) % 4 == 0,
+                    "gemm_w4a8: 16-byte aligned xq rows and wq, 8-byte aligned y rows");
+  const at::DeviceGuard g(y.device());
+  check_rc(atta_gemm_w4a8(y.data_ptr(), xq.data_ptr(), xs.data_ptr<float>(), wq.data_ptr(),
+                          sq.data_ptr<uint8_t>(), static_cast<int>(M), static_cast<int>(N),
+                          static_cast<int>(K), xq.stride(0), y.stride(0),
+                          static_cast<int>(rowmap), static_cast<int>(mode), cur_stream()),
+           "gemm_w4a8");
+}
+
 void fused_lm_head_sample(at::Tensor tokens, at::Tensor keys, const at::Tensor& x,
                           const at::Tensor& w, double eps, const at::Tensor& temperature,
                           const at::Tensor& seeds, const at::Tensor& steps, int64_t finalize,
@@ -1203,6 +1250,8 @@ TORCH_LIBRARY(atta, m) {
         "bool preshuffled=False, Tensor? w_scale=None, int ksplit=1, "
         "Tensor? w_block_scale=None, bool wide_w4=False) -> ()");
   m.def("expand_mxfp4(Tensor(a!) out, Tensor wq, Tensor sq, int rowmap) -> ()");
+  m.def("gemm_w4a8(Tensor(a!) y, Tensor xq, Tensor xs, Tensor wq, Tensor sq, int rowmap, "
+        "int mode) -> ()");
   m.def("set_splitk_workspace(Tensor ws, Tensor counters) -> ()");
   m.def("quant_rows_fp8(Tensor(a!) q, Tensor(b!) scale, Tensor x, Tensor? w, int mode, "
         "float eps, Tensor(c!)? residual=None) -> ()");
@@ -1293,6 +1342,7 @@ TORCH_LIBRARY_IMPL(atta, CUDA, m) {
   m.impl("fused_qkv_rope", &fused_qkv_rope);
   m.impl("fused_gate_up_silu", &fused_gate_up_silu);
   m.impl("expand_mxfp4", &expand_mxfp4);
+  m.impl("gemm_w4a8", &gemm_w4a8);
   m.impl("fused_lm_head_sample", &fused_lm_head_sample);
   m.impl("fused_lm_head_sample_lp", &fused_lm_head_sample_lp);
   m.impl("sample_finalize", &sample_finalize);

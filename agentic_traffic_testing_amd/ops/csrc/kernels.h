@@ -113,6 +113,15 @@ int atta_fused_gate_up_silu(void* out, const void* x, const void* w, int M, int 
 int atta_expand_mxfp4(void* out, const void* codes, const uint8_t* bscale, int N, int K,
                       int64_t out_stride, int rowmap, int dtype, hipStream_t stream);
 
+// MXFP4 W4A8 prefill GEMM (prefill_gemm_w4a8.hip): y = xs * (e4m3 xq [M, K]) . (MXFP4 weight)^T,
+// the weight as N rows of codes / block scales in the layout of ops.preshuffle_mxfp4 with tile
+// row map `rowmap` (0 plain, 1 qkv, 2 silu).  mode 0: y [M, N] bf16 in original row order;
+// mode 2 (rowmap 2): y [M, N / 2] = silu(gate) * up.  ldx in bytes, ldy in elements.
+// K % 128 == 0, N % 32 == 0 (rowmap 1: N % 128 == 0).
+int atta_gemm_w4a8(void* y, const void* xq, const float* xs, const void* codes,
+                   const uint8_t* bscale, int M, int N, int K, int64_t ldx, int64_t ldy,
+                   int rowmap, int mode, hipStream_t stream);
+
 // Split-K workspace of `device` for the skinny GEMVs (fp32 slots + per-tile counters, zeroed).
 int atta_set_splitk_ws(int device, float* ws, int* counters, int64_t ws_floats, int n_counters);
 

@@ -481,6 +481,8 @@ def build_config(args):
         kw["quantization"] = args.quantization
     if getattr(args, "mxfp4_weights_only", False):
         kw["mxfp4_weights_only"] = True
+    if getattr(args, "mxfp4_fp8_activations", False):
+        kw["mxfp4_fp8_activations"] = True
     if getattr(args, "burst_window_ms", None) is not None:
         kw["burst_window_ms"] = args.burst_window_ms
     if getattr(args, "burst_gap_ms", None) is not None:
@@ -568,6 +570,10 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("--mxfp4-weights-only", action="store_true",
                    help="with --quantization mxfp4: keep the layer projections in 4 bits only "
                         "(no 16-bit copies; steps past 128 rows expand into a shared scratch)")
+    p.add_argument("--mxfp4-fp8-activations", action="store_true",
+                   help="with --quantization mxfp4 (W4A8): steps past 128 rows multiply per-token "
+                        "e4m3 activations by the resident 4-bit weights (no 16-bit GEMM; with "
+                        "--mxfp4-weights-only no expand pass and no scratch)")
     p.add_argument("--data-parallel-size", "--dp-size", type=int, default=1,
                    help="engine replicas, one per GPU, behind a router on --port "
                         "(parallel/dp_router.py)")
