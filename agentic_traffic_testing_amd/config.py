@@ -303,6 +303,11 @@ class EngineConfig:
     spec_tokens: int = 3
     spec_ngram_max: int = 4
     spec_ngram_min: int = 2
+    # guided decoding (SamplingParams.guided_regex / guided_choice / guided_json): automaton
+    # states the device pool holds for all live guides together, row 0 included (int16
+    # [guided_pool_states, vocab]: 1.05 GB at the Llama-3 vocabulary), allocated with the first
+    # guided request.  A guide with more states, or one that finds no room, is refused.
+    guided_pool_states: int = 4096
 
     def __post_init__(self):
         if self.quantization not in ("", "fp8", "mxfp4"):

@@ -16,6 +16,7 @@ import numpy as np
 
 from ..config import EngineConfig, resolve_model
 from ..utils import roctx
+from .guided import START, Guide, GuideCompiler
 from .model_runner import ModelRunner
 from .scheduler import Batch, Scheduler
 from .sequence import SamplingParams, Sequence, SeqStatus
@@ -105,6 +106,9 @@ class LLMEngine:
         # and its counters (verify steps run, draft tokens verified, drafts accepted)
         self.proposer: Proposer | None = make_proposer(cfg)
         self.spec_stats = {"verify_steps": 0, "draft_tokens": 0, "accepted_tokens": 0}
+        # guided decoding: the guide compiler and its cache, built with the first guided request
+        self._guides: GuideCompiler | None = None
+        self._guides_lock = threading.Lock()
         # (a TP engine warms up itself once its worker group is fully set up)
         if cfg.startup_warmup and self.runner.is_cuda and not getattr(self, "_defer_warmup",
                                                                       False):
@@ -166,10 +170,30 @@ class LLMEngine:
         if sampling.penalised and self.runner.tp_size > 1:
             raise ValueError("presence_penalty, frequency_penalty, repetition_penalty and "
                              "logit_bias are not served by a tensor-parallel engine")
+        if sampling.guided and self.runner.tp_size > 1:
+            # the automaton states live in one process's device memory, as the counts do
+            raise ValueError("guided_regex, guided_choice and guided_json are not served by a "
+                             "tensor-parallel engine")
+
+    def compile_guide(self, sampling: SamplingParams) -> Guide | None:
+        """The compiled guide of ``sampling`` (None without one), from the cache or compiled
+        now - ``ValueError`` for a pattern or schema outside the dialect, a guide larger than
+        the pool, or ignore_eos with a pattern that can only end.  Thread-safe and free of
+        engine state: the HTTP front end calls it in an executor before it submits a request,
+        so that a compile never runs on the engine thread between two decode steps."""
+        self.check_sampling(sampling)
+        if not sampling.guided:
+            return None
+        with self._guides_lock:
+            if self._guides is None:
+                self._guides = GuideCompiler(
+                    self.tokenizer.token_bytes(), self.model_cfg.vocab_size, self.eos_ids,
+                    max_states=self.cfg.guided_pool_states - 1)
+        return self._guides.compile(sampling)
 
     def add_request(self, request_id: str, prompt_ids, sampling: SamplingParams,
                     arrival_time: float | None = None) -> Sequence:
-        self.check_sampling(sampling)
+        guide = self.compile_guide(sampling)  # (checks the parameters; a cache hit after /chat)
         if sampling.penalised:
             with self.lock:  # device state on first need - here, never inside a graph capture
                 self.runner.ensure_penalty_state()
@@ -184,6 +208,11 @@ class LLMEngine:
             seq.arrival_time = arrival_time
         seq.seed = sampling.seed if sampling.seed is not None else self._rng.getrandbits(62)
         with self.lock:
+            if guide is not None:
+                # device state on first need, then the guide's rows in the pool (ValueError if
+                # it has no room: the request is not queued)
+                self.runner.guide_reserve(seq.seq_id, guide)
+                seq.guide, seq.guide_state = guide, START
             self.scheduler.add(seq)
         return seq
 
@@ -191,10 +220,28 @@ class LLMEngine:
         with self.lock:
             for seq in self.scheduler.abort(request_id):
                 self.runner.penalty_release(seq.seq_id)
+                self.runner.guide_release(seq.seq_id)
 
     def _finish(self, seq: Sequence, reason: str) -> None:
         self.scheduler.finish(seq, reason)
         self.runner.penalty_release(seq.seq_id)  # (a no-op for an unpenalised sequence)
+        self.runner.guide_release(seq.seq_id)    # (and for an unguided one)
+
+    def _guide_step(self, seq: Sequence, tok: int, idx: int) -> bool:
+        """Advance a guided sequence's host shadow state by output token ``idx`` = ``tok``.
+        A token the host table does not allow (the device mask and the host table disagree:
+        a bug, never a property of the model) fails the request: the token and everything after
+        it are dropped, the sequence finishes with reason "error" and False is returned."""
+        if seq.guide is None:
+            return True
+        nxt = seq.guide.advance(seq.guide_state, tok)
+        if nxt >= 0:
+            seq.guide_state = nxt
+            return True
+        del seq.output_ids[idx:]
+        seq._ids_np = None
+        self._finish(seq, "error")
+        return False
 
     def has_unfinished(self) -> bool:
         return self.scheduler.has_work() or self._inflight is not None
@@ -219,6 +266,7 @@ class LLMEngine:
                     batch = self.scheduler.schedule()
                 for seq in batch.preempted:  # re-seeded from its outputs when it comes back
                     self.runner.penalty_release(seq.seq_id)
+                    self.runner.guide_release(seq.seq_id, keep_guide=True)
                 if batch.empty:
                     return []
                 t0 = time.perf_counter()
@@ -293,6 +341,9 @@ class LLMEngine:
             self._record_logprob(seq, idx, lps, row)
             if seq.first_token_time is None:
                 seq.first_token_time = now
+            if not self._guide_step(seq, tok, idx):
+                outs.append(self._output(seq, []))
+                continue
             self.runner.bm.commit(seq.seq_id, seq.token_array(), ncomp)
             reason = self._stop_reason(seq, tok, idx + 1)
             if reason:
@@ -342,6 +393,9 @@ class LLMEngine:
                 self._record_logprob(seq, len(seq.output_ids) - 1, lps, row)
                 if seq.first_token_time is None:
                     seq.first_token_time = now
+                if not self._guide_step(seq, tok, len(seq.output_ids) - 1):
+                    outs.append(self._output(seq, []))
+                    continue
                 self.runner.bm.commit(seq.seq_id, seq.token_array(), seq.num_computed)
                 reason = self._stop_reason(seq, tok)
                 if reason:
@@ -369,6 +423,8 @@ class LLMEngine:
             return None  # logprobs come from plain decode steps (verify rows record none)
         if r._penalised(batch):
             return None  # a verify row's counts would depend on which drafts are accepted
+        if r._guided(batch):
+            return None  # a verify row's automaton state would depend on the rows before it
         max_kv = r.verify_max_kv(S)
         if any(seq.num_tokens > max_kv for seq in batch.seqs):
             return None

@@ -20,6 +20,7 @@ One step = one forward over a decode-first ``Batch`` (scheduler.py) followed by 
 """
 from __future__ import annotations
 
+import collections
 import math
 import os
 import threading
@@ -44,14 +45,16 @@ class MetaLayout:
     """int32-word layout of the packed per-step metadata buffer."""
 
     def __init__(self, T: int, S: int, W: int, NT: int, R: int | None = None,
-                 penalty: bool = False):
+                 penalty: bool = False, guide: bool = False):
         # R: rows the sampler runs over - one per sequence, or every row of a verify step
         # (speculative decoding), whose sampling fields are row-sized
         # penalty: a step of a penalty variant (V_PENALTY) carries four more per-row fields
         # behind the others; every other step's layout is what it was without them
+        # guide: a step of a guide variant (V_GUIDE) carries one more per-row field behind those
         R = S if R is None else R
         self.T, self.S, self.W, self.NT, self.R = T, S, W, NT, R
         self.penalty = bool(penalty)
+        self.guide = bool(guide)
         o = 0
         self.fields = {}
 
@@ -83,6 +86,8 @@ class MetaLayout:
             add("pen_rep", R, torch.float32)    # repetition / frequency / presence penalty
             add("pen_freq", R, torch.float32)
             add("pen_pres", R, torch.float32)
+        if guide:
+            add("guide_slot", R)                # entry of the guide state; < 0: row unguided
         self.size = _even(o)
 
     def views(self, buf: torch.Tensor) -> dict:
@@ -117,15 +122,19 @@ OP_STEP, OP_CAPTURE, OP_STOP, OP_BARRIER = 1, 2, 3, 4
 # step variant (header word 8, third part of a graph key, word 3 of OP_CAPTURE): bit 0 - some
 # row samples with top-k / top-p (logits materialised); bits 1-2 - the logprob mode of the
 # step's most demanding sequence; bit 3 - some sequence has a penalty or a logit bias (logits
-# materialised, penalised into an fp32 buffer before the sampler, token counts updated after)
+# materialised, penalised into an fp32 buffer before the sampler, token counts updated after);
+# bit 4 - some sequence is guided (logits materialised, masked into the fp32 buffer by its
+# automaton state before the sampler, the state advanced after)
 V_TOPKP = 1
 V_PENALTY = 8
+V_GUIDE = 16
 LP_NONE, LP_SAMPLED, LP_TOPN = 0, 1, 2   # no logprobs / the sampled token's / + the top-N
 TOP_N = ops.MAX_TOP_LOGPROBS             # a top-N step computes this many; requests cut theirs
 
 
-def variant_code(topkp: bool, lp_mode: int, penalty: bool = False) -> int:
-    return int(bool(topkp)) | (lp_mode << 1) | (V_PENALTY if penalty else 0)
+def variant_code(topkp: bool, lp_mode: int, penalty: bool = False, guide: bool = False) -> int:
+    return (int(bool(topkp)) | (lp_mode << 1) | (V_PENALTY if penalty else 0)
+            | (V_GUIDE if guide else 0))
 
 
 def variant_lp(variant: int) -> int:
@@ -252,7 +261,7 @@ class ModelRunner:
         # metadata buffers (max layout)
         self.max_layout = MetaLayout(self.max_tokens, self.max_seqs, self.bt_width,
                                      self.max_tokens, max(self.max_seqs, self.ws_rows),
-                                     penalty=True)
+                                     penalty=True, guide=True)
         pin = self.is_cuda
         # two pinned metadata buffers, used alternately: a step's H2D copy may still be queued
         # while the host packs the next step (async look-ahead decode, TP workers); an event
@@ -337,6 +346,17 @@ class ModelRunner:
         self.pen: dict | None = None
         self._pen_slot: dict[int, int] = {}   # seq_id -> slot (seeded)
         self._pen_free: list[int] = []
+        # guided decoding (SamplingParams.guided): device state allocated with the first such
+        # request (ensure_guide_state) - the pool of automaton tables, one current state per
+        # guided running sequence ("slot") - and the host's bookkeeping of both
+        self.guide: dict | None = None
+        self._guide_slots: dict[int, int] = {}    # seq_id -> slot (seeded)
+        self._guide_free: list[int] = []
+        # guides with a range of pool rows, by Guide.key, least recently used first:
+        # {"guide", "base", "refs" (sequences holding it), "uploaded"}
+        self._guide_pool: "collections.OrderedDict[tuple, dict]" = collections.OrderedDict()
+        self._guide_of: dict[int, tuple] = {}     # seq_id -> key of the guide it holds
+        self._f32_logits: torch.Tensor | None = None
 
     # -- sampling penalties ------------------------------------------------------------------
     def ensure_penalty_state(self) -> None:
@@ -356,7 +376,7 @@ class ModelRunner:
             "state": torch.zeros(n, V, dtype=torch.int32, device=dev),
             "bias_ids": torch.full((n, nb), -1, dtype=torch.int32, device=dev),
             "bias_vals": torch.zeros(n, nb, dtype=torch.float32, device=dev),
-            "logits": torch.empty(self.max_seqs, V, dtype=torch.float32, device=dev),
+            "logits": self._sampler_logits(),
         }
         self._pen_free = list(range(n - 1, -1, -1))
 
@@ -401,6 +421,129 @@ class ModelRunner:
         slot = self._pen_slot.pop(seq_id, None)
         if slot is not None:
             self._pen_free.append(slot)
+
+    def _sampler_logits(self) -> torch.Tensor:
+        """The fp32 logits buffer the penalty and the guide kernels write and the sampler
+        reads: one allocation, shared by both features."""
+        if self._f32_logits is None:
+            self._f32_logits = torch.empty(self.max_seqs, self.mcfg.vocab_size,
+                                           dtype=torch.float32, device=self.device)
+        return self._f32_logits
+
+    # -- guided decoding ---------------------------------------------------------------------
+    def ensure_guide_state(self) -> None:
+        """Allocate the guide state on first need - never inside a graph capture (the engine
+        calls this when a guided request is added), never for an engine without one: the pool
+        int16 [guided_pool_states, vocab] of automaton rows (row 0: the shared done state), the
+        int32 [max_num_seqs] current states and the fp32 logits buffer."""
+        if self.guide is not None:
+            return
+        if self.tp_size > 1:
+            raise ValueError("guided decoding is not served under tensor parallelism")
+        n, V, dev = self.cfg.max_num_seqs, self.mcfg.vocab_size, self.device
+        P = int(self.cfg.guided_pool_states)
+        if not 2 <= P <= 32767:
+            raise ValueError(f"guided_pool_states must be in 2 .. 32767, got {P}")
+        print(f"[atta] guided decoding: {P} pool states x {V} tokens, "
+              f"{P * V * 2 / 1e9:.2f} GB of automaton rows", flush=True)
+        self.guide = {
+            # -1 everywhere: an entry nobody uploaded allows nothing and leads to done
+            "next": torch.full((P, V), -1, dtype=torch.int16, device=dev),
+            "state": torch.zeros(n, dtype=torch.int32, device=dev),
+            "logits": self._sampler_logits(),
+            "done_row": False,
+        }
+        self._guide_free = list(range(n - 1, -1, -1))
+
+    def guide_reserve(self, seq_id: int, guide) -> None:
+        """Give ``guide`` a range of pool rows (host bookkeeping: first fit over the gaps
+        between the reserved ranges, whole guides no sequence holds evicted least recently
+        used first) and count ``seq_id`` among its holders.  ``ValueError`` if the pool has no
+        room.  Nothing is uploaded here: ``_guide_slot`` does that on the step stream."""
+        self.ensure_guide_state()
+        pool, P = self._guide_pool, self.guide["next"].shape[0]
+        ent = pool.get(guide.key)
+        if ent is None:
+            need = guide.num_states
+            while True:
+                base = self._guide_fit(need, P)
+                if base is not None:
+                    break
+                victim = next((k for k, e in pool.items() if e["refs"] == 0), None)
+                if victim is None:
+                    raise ValueError(f"no room for a guide of {need} states in the guide pool "
+                                     f"({P - 1} states, guided_pool_states): every other guide "
+                                     "is in use by a running request")
+                del pool[victim]
+            ent = pool[guide.key] = {"guide": guide, "base": base, "refs": 0, "uploaded": False}
+        pool.move_to_end(guide.key)
+        ent["refs"] += 1
+        self._guide_of[seq_id] = guide.key
+
+    def _guide_fit(self, need: int, P: int) -> int | None:
+        at = 1  # row 0 is the done state
+        for e in sorted(self._guide_pool.values(), key=lambda e: e["base"]):
+            if e["base"] - at >= need:
+                return at
+            at = e["base"] + e["guide"].num_states
+        return at if P - at >= need else None
+
+    def _guide_slot(self, seq) -> int:
+        """The slot of a guided sequence whose next token this step samples; a sequence without
+        one (just admitted, or re-admitted after a preemption) gets a free slot, seeded on the
+        current stream with the pool row of its host shadow state - so a recomputed sequence
+        continues mid-pattern.  The guide's rows are uploaded here, on the same stream, the
+        first time one of its sequences needs them."""
+        slot = self._guide_slots.get(seq.seq_id)
+        if slot is None:
+            if not self._guide_free:  # running sequences <= max_num_seqs, each holds at most one
+                raise RuntimeError("no free guide slot: a finished, aborted or preempted "
+                                   "sequence was not released")
+            ent = self._guide_pool[self._guide_of[seq.seq_id]]
+            g, base, dev = ent["guide"], ent["base"], self.guide
+            if not dev["done_row"]:   # row 0 is the same in every guide's table
+                dev["next"][0].copy_(torch.from_numpy(g.next[0]))
+                dev["done_row"] = True
+            if not ent["uploaded"]:
+                # local rows 1 .. n -> pool rows base .. base + n - 1; 0 (done) and -1 stay
+                t = g.next[1:]
+                rows = torch.from_numpy(np.where(t > 0, t + np.int16(base - 1), t))
+                dev["next"][base:base + g.num_states].copy_(rows)
+                ent["uploaded"] = True
+            slot = self._guide_free.pop()
+            st = int(seq.guide_state)
+            ops.guide_seed(dev["state"], slot, st + base - 1 if st > 0 else 0)
+            self._guide_slots[seq.seq_id] = slot
+        return slot
+
+    def guide_release(self, seq_id: int, keep_guide: bool = False) -> None:
+        """Give a finished, aborted or preempted sequence's slot back, and (unless
+        ``keep_guide``: a preempted sequence comes back) drop its hold on its guide's pool rows
+        (host bookkeeping only; nothing is launched).  Neither the slot's state word nor the
+        pool rows are touched here, and kernels already queued may still read them - safe, by
+        the stream-order argument of ``penalty_release``: every step, every seed, every upload
+        and every graph replay is ordered on one stream, so
+
+        * a look-ahead step queued behind an end token reads the slot's state (0, done: the
+          step before advanced it there), masks its row to the end tokens and advances 0 -> 0;
+          its token is discarded by the engine.  A look-ahead step of a sequence cut by length
+          or aborted advances a state nobody owns any more;
+        * the next owner's first use of a slot is its seed, queued behind every step that
+          carried the old owner: those steps saw the old state, the new owner's first apply
+          sees exactly its seed;
+        * rows of an evicted guide are rewritten by the next guide's upload, queued behind
+          every step of the sequences that held the old one (it had no holder left, so no later
+          step reads them); until then nothing refers to them.
+
+        A preempted sequence comes back through ``_guide_slot``, which seeds its slot from the
+        host shadow state (``Sequence.guide_state``, advanced with every appended token)."""
+        slot = self._guide_slots.pop(seq_id, None)
+        if slot is not None:
+            self._guide_free.append(slot)
+        if not keep_guide:
+            key = self._guide_of.pop(seq_id, None)
+            if key is not None:
+                self._guide_pool[key]["refs"] -= 1
 
     def _room_for_decode_copies(self) -> bool:
         """The pre-shuffled decode copies double the 16-bit weights (16 GB for Llama-3.1-8B);
@@ -501,7 +644,8 @@ class ModelRunner:
         S = d["seq_kvlen"].shape[0]
         NT = d["tile_seq"].shape[0]
         penalty = self._penalised(batch)
-        lay = MetaLayout(T, S, self.bt_width, NT, penalty=penalty)
+        guide = self._guided(batch)
+        lay = MetaLayout(T, S, self.bt_width, NT, penalty=penalty, guide=guide)
         input_ids = np.zeros(T, dtype=np.int32)
         row = 0
         temps = np.zeros(S, dtype=np.float32)
@@ -537,6 +681,14 @@ class ModelRunner:
                     freq[i] = sp.frequency_penalty
                     pres[i] = sp.presence_penalty
             arrays.update(pen_slot=slot, pen_rep=rep, pen_freq=freq, pen_pres=pres)
+        if guide:
+            # per sampled row: the sequence's slot, only where this step samples its next token
+            # (as above); unguided and padded rows carry -1 and are copied through
+            slot = np.full(S, -1, dtype=np.int32)
+            for i, (seq, s0, n) in enumerate(zip(batch.seqs, batch.q_start, batch.q_len)):
+                if seq.guide is not None and s0 + n == seq.num_tokens:
+                    slot[i] = self._guide_slot(seq)
+            arrays.update(guide_slot=slot)
         return lay, arrays
 
     @property
@@ -592,7 +744,8 @@ class ModelRunner:
         top-p / top-k (logits are materialised and the top-k / top-p kernel samples every
         row); bits 1-2 - the step's logprob mode, whose results land in ws["lp"] (and
         ws["top_ids"] / ws["top_lp"]), one row per sampled row; bit 3 - some sequence is
-        penalised (logits materialised, ``LlamaModel.sample_logits``' penalty tail)."""
+        penalised (logits materialised, ``LlamaModel.sample_logits``' penalty tail); bit 4 - some
+        sequence is guided (logits materialised, its guide tail)."""
         m = self.model
         T = v["input_ids"].shape[0]
         special = bool(variant & V_TOPKP)
@@ -605,9 +758,15 @@ class ModelRunner:
         if variant & V_PENALTY:
             pen = {**self.pen, "slot": v["pen_slot"], "rep": v["pen_rep"],
                    "freq": v["pen_freq"], "pres": v["pen_pres"]}
-        # logits are materialised for top-k / top-p, penalties and for every logprob the fused
-        # sampler cannot record
-        mat = special or pen is not None or (lp_mode != LP_NONE and not lp_fused)
+        # guide variant: ops.guide_apply masks the (penalised) logits by each row's automaton
+        # state, ops.guide_advance moves the state by the sampled token
+        gd = None
+        if variant & V_GUIDE:
+            gd = {**self.guide, "slot": v["guide_slot"]}
+        # logits are materialised for top-k / top-p, penalties, guides and for every logprob
+        # the fused sampler cannot record
+        mat = (special or pen is not None or gd is not None
+               or (lp_mode != LP_NONE and not lp_fused))
         # alternatives a materialised logprob step computes (None: no logprobs)
         lp_top = None if lp_mode == LP_NONE else (TOP_N if lp_mode == LP_TOPN else 0)
         if (self.fused_decode and md.num_tiles == 0
@@ -620,7 +779,7 @@ class ModelRunner:
                                     ws, v["temperature"], v["seeds"], v["steps"],
                                     prev_tokens=self.ws["tokens"], feed_prev=v["feed_prev"],
                                     top_p=v["top_p"] if special else None, top_k=v["top_k"],
-                                    lp_top=lp_top, lp_fused=lp_fused, penalty=pen)
+                                    lp_top=lp_top, lp_fused=lp_fused, penalty=pen, guide=gd)
         decode_only = md.num_tiles == 0 and md.num_decode == T
         # final norm on the sampled rows only (each sequence's last token)
         last = m.forward(v["input_ids"], md, self.k_layers, self.v_layers, self.part_out,
@@ -639,7 +798,7 @@ class ModelRunner:
         out = self.ws["tokens"][:logits.shape[0]] if decode_only else None
         toks = m.sample_logits(logits, v["temperature"], v["seeds"], v["steps"],
                                top_p=v["top_p"] if special else None, top_k=v["top_k"],
-                               out=out, penalty=pen)
+                               out=out, penalty=pen, guide=gd)
         if lp_top is not None:
             m.logits_logprobs(logits, toks, lp_top, self.ws)
         return toks
@@ -683,9 +842,14 @@ class ModelRunner:
     def _penalised(batch: Batch) -> bool:
         return any(s.sampling.penalised for s in batch.seqs)
 
+    @staticmethod
+    def _guided(batch: Batch) -> bool:
+        return any(s.guide is not None for s in batch.seqs)
+
     @classmethod
     def _variant(cls, batch: Batch) -> int:
-        return variant_code(cls._special(batch), cls._lp_mode(batch), cls._penalised(batch))
+        return variant_code(cls._special(batch), cls._lp_mode(batch), cls._penalised(batch),
+                            cls._guided(batch))
 
     def _fetch_logprobs(self, variant: int, n: int):
         """Synchronous copy of a step's logprob arrays (eager steps, after the tokens')."""
@@ -949,7 +1113,8 @@ class ModelRunner:
             self.graphs[key].replay()
             self.graph_steps += 1
             return io["out"]
-        lay = MetaLayout(T, S, W, NT, penalty=bool(variant & V_PENALTY))
+        lay = MetaLayout(T, S, W, NT, penalty=bool(variant & V_PENALTY),
+                         guide=bool(variant & V_GUIDE))
         dev = self.meta_dev[:size]
         self._h2d(dev, size)
         v = lay.views(dev)
@@ -1025,7 +1190,8 @@ class ModelRunner:
     def capture(self, bucket: int, parts: int | None = None, variant: int = 0):
         """Capture a decode step for `bucket` sequences whose contexts fit `parts` attention
         partitions (default: max_model_len) into a hipGraph; ``variant`` (variant_code): the
-        top-k / top-p sampler (logits materialised), a logprob mode and / or the penalty tail.
+        top-k / top-p sampler (logits materialised), a logprob mode, the penalty and / or the guide
+        tail.
         Variants other than 0 are captured on first use."""
         variant = int(variant)
         parts = parts or self._tier(bucket)[1]
@@ -1036,7 +1202,10 @@ class ModelRunner:
         penalty = bool(variant & V_PENALTY)
         if penalty:
             self.ensure_penalty_state()  # (allocated with the request: a no-op here)
-        lay = MetaLayout(bucket, bucket, self.bt_width, 0, penalty=penalty)
+        guide = bool(variant & V_GUIDE)
+        if guide:
+            self.ensure_guide_state()    # (allocated with the request: a no-op here)
+        lay = MetaLayout(bucket, bucket, self.bt_width, 0, penalty=penalty, guide=guide)
         dev = torch.zeros(lay.size, dtype=torch.int32, device=self.device)
         v = lay.views(dev)
         # dummy sequences: kvlen 0, slot -1 -> kernels skip them
@@ -1044,6 +1213,8 @@ class ModelRunner:
         v["slot_mapping"].fill_(-1)
         if penalty:  # no penalty slot either: the warm-up and capture passes count nothing
             v["pen_slot"].fill_(-1)
+        if guide:    # nor a guide slot: they advance nothing
+            v["guide_slot"].fill_(-1)
         v["logits_idx"].copy_(torch.arange(bucket, dtype=torch.int64))
         md = self._meta(v, bucket, 0)
         # a capture may come between look-ahead steps (a new partition bucket mid-generation):
@@ -1170,5 +1341,5 @@ class ModelRunner:
 
 
 __all__ = ["ModelRunner", "MetaLayout", "ref", "HDR_WORDS", "OP_STEP", "OP_CAPTURE", "OP_STOP",
-           "OP_BARRIER", "LP_NONE", "LP_SAMPLED", "LP_TOPN", "TOP_N", "V_PENALTY", "variant_code",
-           "variant_lp"]
+           "OP_BARRIER", "LP_NONE", "LP_SAMPLED", "LP_TOPN", "TOP_N", "V_PENALTY", "V_GUIDE",
+           "variant_code", "variant_lp"]

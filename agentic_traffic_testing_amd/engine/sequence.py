@@ -41,6 +41,21 @@ class SamplingParams:
     frequency_penalty: float = 0.0     # in [-2, 2]
     repetition_penalty: float = 1.0    # > 0
     logit_bias: dict | None = None     # {token id: bias in [-100, 100]}, <= 300 entries
+    # Guided decoding (at most one; defaults: off): the generated text must full-match the
+    # regex / be one of the strings / be an instance of the JSON schema in canonical form
+    # (engine/guided.py: dialect, schema subset).  Tokens the guide's automaton does not allow
+    # are masked to -inf after the penalties and before temperature, noise and top-k / top-p;
+    # the end token is allowed exactly where the text so far is a complete match.  Logprobs
+    # stay raw.  With ignore_eos the guide never allows an end token.
+    guided_regex: str | None = None
+    guided_choice: list | None = None
+    guided_json: dict | str | None = None
+
+    @property
+    def guided(self) -> bool:
+        """Is one of the guide fields set?"""
+        return (self.guided_regex is not None or self.guided_choice is not None
+                or self.guided_json is not None)
 
     @property
     def penalised(self) -> bool:
@@ -63,6 +78,10 @@ class SamplingParams:
         v = self.repetition_penalty
         if not _is_number(v) or not v > 0.0:
             raise ValueError(f"repetition_penalty must be a finite number > 0, got {v!r}")
+        if self.guided:
+            from .guided import guide_spec
+
+            guide_spec(self)   # one field at most, each of its type
         lb = self.logit_bias
         if lb is None:
             return
@@ -120,6 +139,10 @@ class Sequence:
     # (logprobs >= 1) the position's [(id, logprob), ...] alternatives
     logprobs: list | None = None
     top_logprobs: list | None = None
+    # guided decoding: the compiled guide (engine/guided.py) and the host's shadow of the
+    # automaton state - the table row after every token appended so far
+    guide: object | None = None
+    guide_state: int = 1
     _ids_np: np.ndarray | None = None
 
     @property

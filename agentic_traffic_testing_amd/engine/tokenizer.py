@@ -119,6 +119,11 @@ class SyntheticTokenizer:
     def count(self, text: str) -> int:
         return len(self.encode(text))
 
+    def token_bytes(self) -> list:
+        """Every token's bytes by id, None for the special tokens (guided decoding walks its
+        automaton over these)."""
+        return list(self._id_to_piece) + [None] * self.num_special
+
     def random_ids(self, n: int, rng: np.random.Generator) -> list[int]:
         """n ordinary (word-like) token ids, for synthetic prompts of exact length."""
         lo = 256
@@ -205,8 +210,36 @@ class HFTokenizer:
     def count(self, text):
         return len(self.encode(text))
 
+    def token_bytes(self) -> list:
+        """Every token's bytes by id, None for special (added) tokens: a byte-level BPE
+        vocabulary spells each byte as one printable character, inverted here."""
+        u2b = {c: b for b, c in _bytes_to_unicode().items()}
+        special = set(self._tok.get_added_tokens_decoder())
+        out: list = [None] * self.vocab_size
+        for tok, i in self._tok.get_vocab(with_added_tokens=True).items():
+            if i in special or not 0 <= i < self.vocab_size:
+                continue
+            try:
+                out[i] = bytes(u2b[c] for c in tok)
+            except KeyError:    # not a byte-level piece: leave it out of every guide
+                out[i] = None
+        return out
+
     def random_ids(self, n, rng):
         return rng.integers(1000, min(self.vocab_size, 128000), size=n).tolist()
+
+
+def _bytes_to_unicode() -> dict:
+    """GPT-2's byte -> printable character map of byte-level BPE vocabularies: the printable
+    Latin-1 bytes stand for themselves, the others are numbered from U+0100 up."""
+    keep = [*range(ord("!"), ord("~") + 1), *range(0xA1, 0xAD), *range(0xAE, 0x100)]
+    out = {b: chr(b) for b in keep}
+    n = 0
+    for b in range(256):
+        if b not in out:
+            out[b] = chr(256 + n)
+            n += 1
+    return out
 
 
 def get_tokenizer(model: str | None = None, vocab_size: int = 128256):

@@ -695,7 +695,8 @@ class LlamaModel:
                        temperature, seeds, steps, prev_tokens=None,
                        feed_prev=None, top_p=None, top_k=None, max_qlen: int = 1,
                        min_qlen: int = 1, lp_top: int | None = None,
-                       lp_fused: bool = False, penalty: dict | None = None) -> torch.Tensor:
+                       lp_fused: bool = False, penalty: dict | None = None,
+                       guide: dict | None = None) -> torch.Tensor:
         """Fused decode step; returns sampled ids, one per row.  Every sequence has one query
         row - or, in a verify step of speculative decoding (``max_qlen`` > 1: the longest of
         the batch), sequence s of ``md.num_decode`` has the rows ``md.seq_qstart[s]`` ..
@@ -717,8 +718,9 @@ class LlamaModel:
         logits through ``ops.token_logprobs`` with its ``lp_top`` alternatives in
         ws["top_ids"] / ws["top_lp"].
 
-        ``penalty`` (see ``sample_logits``): the logits are materialised as for top-k / top-p
-        and sampled through the penalty tail; logprobs still read the raw logits."""
+        ``penalty`` / ``guide`` (see ``sample_logits``): the logits are materialised as for
+        top-k / top-p and sampled through the penalty / guide tail; logprobs still read the raw
+        logits."""
         eps = self.cfg.rms_norm_eps
         nq, nkv = self.n_heads, self.n_kv_heads
         B = input_ids.shape[0]
@@ -752,10 +754,12 @@ class LlamaModel:
             ops.decode_gate_up_silu(residual, eps=eps, out=act,
                                     **self._decode_w(L, "gate_up", B))
             self._row_parallel(act, L, "down", residual)
-        if top_p is not None or penalty is not None or (lp_top is not None and not lp_fused):
+        if top_p is not None or penalty is not None or guide is not None or \
+                (lp_top is not None and not lp_fused):
             logits = self.compute_logits(ops.rms_norm(residual, self.norm, eps))
             toks = self.sample_logits(logits, temperature, seeds, steps, top_p=top_p,
-                                      top_k=top_k, out=ws["tokens"][:B], penalty=penalty)
+                                      top_k=top_k, out=ws["tokens"][:B], penalty=penalty,
+                                      guide=guide)
             if lp_top is not None:
                 self.logits_logprobs(logits, toks, lp_top, ws)
             return toks
@@ -764,25 +768,35 @@ class LlamaModel:
 
     @staticmethod
     def sample_logits(logits: torch.Tensor, temperature, seeds, steps, top_p=None, top_k=None,
-                      out=None, penalty: dict | None = None) -> torch.Tensor:
+                      out=None, penalty: dict | None = None,
+                      guide: dict | None = None) -> torch.Tensor:
         """Sample one token per materialised ``logits`` row: the top-k / top-p kernel with
         ``top_p`` (per-row device tensors), else the plain sampler.  ``penalty`` (the runner's
         penalty state plus this step's per-row "slot" / "rep" / "freq" / "pres"): the sampler
         reads ``ops.penalty_apply``'s fp32 rows instead of the raw ones and
         ``ops.penalty_update`` then counts the sampled tokens - apply, sample, update, all on
-        device-side parameters, so the tail is captured with the step."""
+        device-side parameters, so the tail is captured with the step.  ``guide`` (the runner's
+        guide state plus this step's per-row "slot"): ``ops.guide_apply`` masks the rows - the
+        penalised ones in place, else the raw ones into the fp32 buffer - by each row's
+        automaton state and ``ops.guide_advance`` moves the states by the sampled tokens.  The
+        order: penalty_apply, guide_apply, sampler, penalty_update, guide_advance."""
         src = logits
         if penalty is not None:
             src = ops.penalty_apply(penalty["logits"][:logits.shape[0]], logits,
                                     penalty["state"], penalty["slot"], penalty["rep"],
                                     penalty["freq"], penalty["pres"], penalty["bias_ids"],
                                     penalty["bias_vals"])
+        if guide is not None:
+            src = ops.guide_apply(guide["logits"][:logits.shape[0]], src, guide["next"],
+                                  guide["state"], guide["slot"])
         if top_p is not None:
             toks = ops.sample_topkp(src, temperature, top_p, top_k, seeds, steps, out=out)
         else:
             toks = ops.sample(src, temperature, seeds, steps, out=out)
         if penalty is not None:
             ops.penalty_update(penalty["state"], penalty["slot"], toks)
+        if guide is not None:
+            ops.guide_advance(guide["state"], guide["next"], guide["slot"], toks)
         return toks
 
     @staticmethod

@@ -1205,6 +1205,32 @@ def penalty_update(state, row_slot, tokens):
     _native().penalty_update(state, row_slot, tokens)
 
 
+def guide_apply(out, logits, next_table, state, row_slot):
+    """``out`` [R, V] fp32 <- the masked logits of ``logits`` [R, V] (bf16 / fp16 / fp32, any row
+    stride; may be ``out`` itself, fp32): row r with slot s = row_slot[r] in [0, slots) reads
+    its pool state st = state[s] and gets -inf wherever next_table[st][v] < 0 (csrc/guided.hip);
+    any other row is the raw logits in fp32.  Every parameter is a device tensor
+    (graph-capturable)."""
+    if not logits.is_cuda:
+        return ref.guide_apply(out, logits, next_table, state, row_slot)
+    _native().guide_apply(out, logits, next_table, state, row_slot)
+    return out
+
+
+def guide_advance(state, next_table, row_slot, tokens):
+    """state[row_slot[r]] <- next_table[state[row_slot[r]]][tokens[r]] for the rows with a slot
+    (after the sampler); a disallowed or out-of-range token leads to state 0."""
+    if not state.is_cuda:
+        return ref.guide_advance(state, next_table, row_slot, tokens)
+    _native().guide_advance(state, next_table, row_slot, tokens)
+
+
+def guide_seed(state, slot: int, value: int):
+    """state[slot] <- value: one int32, ordered on the current stream (admission and
+    re-admission of a guided sequence; never inside a graph)."""
+    state[slot:slot + 1].fill_(int(value))
+
+
 def decode_lm_head_sample(x, w, eps, temperature, seeds, steps, keys, tokens=None,
                           finalize=True, vocab_offset=0, preshuffled=False, logprobs=None,
                           lp_ws=None):

@@ -503,6 +503,80 @@ void penalty_update(at::Tensor state, const at::Tensor& row_slot, const at::Tens
            "penalty_update");
 }
 
+// ---- guided decoding (guided.hip) -------------------------------------------------------------
+// next [pool_states, vocab] int16 contiguous, state [slots] int32 contiguous, one device
+void check_guide_state(const at::Tensor& next, const at::Tensor& state, const char* op) {
+  check_dev(next, "next");
+  TORCH_CHECK(next.dim() == 2 && next.scalar_type() == at::kShort && next.is_contiguous() &&
+                  next.size(0) >= 1 && next.size(0) <= 32767 && next.size(1) > 0 &&
+                  next.size(1) <= (int64_t{1} << 30),
+              op, ": next must be a contiguous int16 [pool_states <= 32767, vocab] tensor");
+  TORCH_CHECK(state.dim() == 1 && state.scalar_type() == at::kInt && state.is_contiguous() &&
+                  state.numel() < (int64_t{1} << 31) && state.device() == next.device(),
+              op, ": state must be a contiguous int32 [slots] tensor on next's device");
+}
+
+// The vector path needs 16-byte aligned row pointers and vocab % 8 == 0 and is chosen per row in
+// the kernel; any element-aligned base and stride is served element by element.
+void guide_apply(at::Tensor out, const at::Tensor& logits, const at::Tensor& next,
+                 const at::Tensor& state, const at::Tensor& row_slot) {
+  check_dev(logits, "logits");
+  check_guide_state(next, state, "guide_apply");
+  const int64_t rows = logits.dim() == 2 ? logits.size(0) : -1, vocab = next.size(1);
+  TORCH_CHECK(rows >= 0 && logits.size(1) == vocab && (vocab == 1 || logits.stride(1) == 1) &&
+                  logits.stride(0) >= 0,
+              "guide_apply: logits [rows, vocab] with unit column stride");
+  TORCH_CHECK(out.dim() == 2 && out.scalar_type() == at::kFloat && out.size(0) == rows &&
+                  out.size(1) == vocab && (vocab == 1 || out.stride(1) == 1) &&
+                  (rows <= 1 || out.stride(0) >= vocab),
+              "guide_apply: out must be fp32 [rows, vocab] with unit column stride");
+  int dt = 2;
+  if (logits.scalar_type() == at::kBFloat16) dt = 0;
+  else if (logits.scalar_type() == at::kHalf) dt = 1;
+  else TORCH_CHECK(logits.scalar_type() == at::kFloat, "guide_apply: logits bf16 / fp16 / fp32");
+  TORCH_CHECK(reinterpret_cast<uintptr_t>(logits.data_ptr()) % logits.element_size() == 0 &&
+                  reinterpret_cast<uintptr_t>(out.data_ptr()) % 4 == 0,
+              "guide_apply: logits and out must start aligned to their element size");
+  // in place (after penalty_apply): the same fp32 elements exactly; any other overlap would
+  // have one lane read what another writes
+  const bool same = logits.data_ptr() == out.data_ptr();
+  TORCH_CHECK(!same || (dt == 2 && (rows <= 1 || logits.stride(0) == out.stride(0))),
+              "guide_apply: in place takes fp32 logits with out's row stride");
+  TORCH_CHECK(row_slot.scalar_type() == at::kInt && row_slot.is_contiguous() &&
+                  row_slot.numel() >= rows,
+              "guide_apply: row_slot int32, one per row");
+  TORCH_CHECK(next.device() == logits.device() && out.device() == logits.device() &&
+                  row_slot.device() == logits.device(),
+              "guide_apply: one device");
+  TORCH_CHECK(rows <= 65535, "guide_apply: at most 65535 rows");
+  const at::DeviceGuard g(logits.device());
+  check_rc(atta_guide_apply(out.data_ptr<float>(), rows > 1 ? out.stride(0) : vocab,
+                            logits.data_ptr(), rows > 1 ? logits.stride(0) : vocab, dt,
+                            next.data_ptr<int16_t>(), static_cast<int>(rows),
+                            static_cast<int>(vocab), static_cast<int>(next.size(0)),
+                            state.data_ptr<int>(), static_cast<int>(state.numel()),
+                            row_slot.data_ptr<int>(), cur_stream()),
+           "guide_apply");
+}
+
+void guide_advance(at::Tensor state, const at::Tensor& next, const at::Tensor& row_slot,
+                   const at::Tensor& tokens) {
+  check_guide_state(next, state, "guide_advance");
+  TORCH_CHECK(row_slot.scalar_type() == at::kInt && tokens.scalar_type() == at::kLong &&
+                  row_slot.is_contiguous() && tokens.is_contiguous() &&
+                  row_slot.numel() >= tokens.numel() && tokens.numel() < (int64_t{1} << 31),
+              "guide_advance: row_slot int32 and tokens int64, one per row");
+  TORCH_CHECK(row_slot.device() == state.device() && tokens.device() == state.device(),
+              "guide_advance: one device");
+  const at::DeviceGuard g(state.device());
+  check_rc(atta_guide_advance(state.data_ptr<int>(), next.data_ptr<int16_t>(),
+                              static_cast<int>(next.size(1)), static_cast<int>(next.size(0)),
+                              static_cast<int>(state.numel()), row_slot.data_ptr<int>(),
+                              tokens.data_ptr<int64_t>(), static_cast<int>(tokens.numel()),
+                              cur_stream()),
+           "guide_advance");
+}
+
 // fp8 weight-only quantisation: w is uint8 (OCP e4m3fn bytes, pre-shuffled in 16 x 64 blocks)
 // and w_scale the fp32 per-row dequant scale; returns the scale pointer (nullptr: 16-bit w).
 const float* fp8_scale(const at::Tensor& w, const c10::optional<at::Tensor>& w_scale,
@@ -1314,6 +1388,9 @@ TORCH_LIBRARY(atta, m) {
   m.def("penalty_apply(Tensor(a!) out, Tensor logits, Tensor state, Tensor row_slot, Tensor rep, "
         "Tensor freq, Tensor pres, Tensor bias_ids, Tensor bias_vals) -> ()");
   m.def("penalty_update(Tensor(a!) state, Tensor row_slot, Tensor tokens) -> ()");
+  m.def("guide_apply(Tensor(a!) out, Tensor logits, Tensor next, Tensor state, "
+        "Tensor row_slot) -> ()");
+  m.def("guide_advance(Tensor(a!) state, Tensor next, Tensor row_slot, Tensor tokens) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(atta, CUDA, m) {
@@ -1337,6 +1414,8 @@ TORCH_LIBRARY_IMPL(atta, CUDA, m) {
   m.impl("penalty_seed", &penalty_seed);
   m.impl("penalty_apply", &penalty_apply);
   m.impl("penalty_update", &penalty_update);
+  m.impl("guide_apply", &guide_apply);
+  m.impl("guide_advance", &guide_advance);
   m.impl("skinny_gemm", &skinny_gemm);
   m.impl("prefill_gemm", &prefill_gemm);
   m.impl("fused_qkv_rope", &fused_qkv_rope);

@@ -84,6 +84,16 @@ int atta_penalty_apply(float* out, int64_t out_stride, const void* logits, int64
 int atta_penalty_update(int* state, int vocab, int num_slots, const int* row_slot,
                         const int64_t* tokens, int rows, hipStream_t stream);
 
+// guided decoding (guided.hip): next [pool_states, vocab] int16 (the pool state after a token,
+// -1: not allowed), state [slots] int32.  logits_dtype: 0 bf16, 1 fp16, 2 fp32; logits may be
+// out itself (fp32, same stride); rows with a slot outside [0, slots) are copied through as fp32
+int atta_guide_apply(float* out, int64_t out_stride, const void* logits, int64_t logits_stride,
+                     int logits_dtype, const int16_t* next, int rows, int vocab, int pool_states,
+                     const int* state, int num_slots, const int* row_slot, hipStream_t stream);
+int atta_guide_advance(int* state, const int16_t* next, int vocab, int pool_states,
+                       int num_slots, const int* row_slot, const int64_t* tokens, int rows,
+                       hipStream_t stream);
+
 int atta_skinny_gemm_push(const void* x, const void* w, int M, int N, int K, int64_t x_stride,
                           int waves, int ksplit, const float* wscale, int dtype,
                           void* const* bases, int rank, int world, int64_t max_elems,

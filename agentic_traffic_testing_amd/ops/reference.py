@@ -113,6 +113,12 @@ def paged_attention(q, k_cache, v_cache, block_tables, seq_kvlen, seq_qstart, sc
     return out
 
 
+def _nan_loses(sc: torch.Tensor) -> torch.Tensor:
+    """A masked logit (-inf, guided decoding) plus the +inf Gumbel draw is NaN: the kernels'
+    comparison never selects it, while torch.argmax would take it for the maximum."""
+    return torch.where(torch.isnan(sc), torch.full_like(sc, float("-inf")), sc)
+
+
 def _sample_scores(lf: torch.Tensor, r: int, temperature, seeds, steps, vocab_offset: int):
     t = float(temperature[r])
     if not t > 1e-5:
@@ -129,7 +135,7 @@ def sample(logits: torch.Tensor, temperature: torch.Tensor, seeds: torch.Tensor,
     out = torch.empty(lf.shape[0], dtype=torch.long, device=logits.device)
     for r in range(lf.shape[0]):
         sc = _sample_scores(lf, r, temperature, seeds, steps, vocab_offset)
-        out[r] = int(torch.argmax(sc)) + vocab_offset
+        out[r] = int(torch.argmax(_nan_loses(sc))) + vocab_offset
     return out
 
 
@@ -168,7 +174,7 @@ def sample_topkp(logits: torch.Tensor, temperature, top_p, top_k, seeds,
         idx = torch.arange(V, dtype=torch.int64)
         sc = x + gumbel_noise(int(seeds[r]), int(steps[r]), idx)
         sc = torch.where(keep, sc, torch.tensor(float("-inf")))
-        out[r] = int(torch.argmax(sc))
+        out[r] = int(torch.argmax(_nan_loses(sc)))
     return out.to(logits.device)
 
 
@@ -246,6 +252,37 @@ def penalty_update(state: torch.Tensor, row_slot, tokens) -> None:
         s, t = int(row_slot[r]), int(tokens[r])
         if s >= 0 and 0 <= t < state.shape[1]:
             state[s, t] += 1
+
+
+# ---- guided decoding (ops/csrc/guided.hip) ---------------------------------------------------
+def _guide_state(state: torch.Tensor, next_table: torch.Tensor, slot: int) -> int:
+    """The slot's current pool state, clamped into the pool as the kernels clamp it."""
+    return min(max(int(state[slot]), 0), next_table.shape[0] - 1)
+
+
+def guide_apply(out: torch.Tensor, logits: torch.Tensor, next_table: torch.Tensor,
+                state: torch.Tensor, row_slot):
+    """out[r][v] = -inf where next_table[state[row_slot[r]]][v] < 0, else float(logits[r][v]);
+    rows whose slot is outside [0, slots) are the raw logits in fp32.  ``logits`` may be ``out``."""
+    for r in range(logits.shape[0]):
+        s = int(row_slot[r])
+        l = logits[r].float().clone()
+        if 0 <= s < state.shape[0]:
+            l[next_table[_guide_state(state, next_table, s)] < 0] = float("-inf")
+        out[r].copy_(l)
+    return out
+
+
+def guide_advance(state: torch.Tensor, next_table: torch.Tensor, row_slot, tokens) -> None:
+    """state[slot] = next_table[state[slot]][token] for every row with a slot; a disallowed or
+    out-of-range token leads to state 0 (done)."""
+    for r in range(tokens.shape[0]):
+        s, t = int(row_slot[r]), int(tokens[r])
+        if not 0 <= s < state.shape[0]:
+            continue
+        n = int(next_table[_guide_state(state, next_table, s), t]) \
+            if 0 <= t < next_table.shape[1] else -1
+        state[s] = n if 0 <= n < next_table.shape[0] else 0
 
 
 def lm_head_sample_logprobs(x: torch.Tensor, w: torch.Tensor, eps: float, temperature, seeds,

@@ -4,7 +4,8 @@ API-compatible with the reference's aiohttp front end over vLLM (llm/serve_llm.p
 
 * ``POST /chat | /completion | /generate`` with ``{prompt|input, max_tokens?, request_id?,
   system_prompt?, skip_chat_template?, logprobs?, presence_penalty?, frequency_penalty?,
-  repetition_penalty?, logit_bias?}`` -> ``{"output", "meta": {request_id,
+  repetition_penalty?, logit_bias?, guided_regex? | guided_choice? | guided_json?}`` ->
+  ``{"output", "meta": {request_id,
   latency_ms, queue_wait_s, prompt_tokens, completion_tokens, total_tokens, otel}}`` (with an
   integer ``logprobs`` also ``"logprobs": {tokens, token_ids, token_logprobs,
   top_logprobs}``, one entry per generated token); 400 on bad JSON /
@@ -233,6 +234,23 @@ async def handle_chat(request: web.Request) -> web.Response:
         except ValueError as exc:
             _leave()
             return web.json_response({"error": str(exc)}, status=400)
+        # optional guide: "guided_regex" (string), "guided_choice" (list of strings) or
+        # "guided_json" (schema object or its text), one at most; absent: nothing changes.  The
+        # guide is compiled here, in an executor, BEFORE the request is submitted, so that a
+        # compile never runs on the engine thread between two decode steps (add_request then
+        # finds it in the cache).  A bad value is a 400 with the compiler's own message
+        guide_kw = {k: data[k] for k in GUIDE_KEYS if data.get(k) is not None}
+        if guide_kw:
+            probe = SamplingParams(
+                ignore_eos=bool(data.get("ignore_eos", st.s.ignore_eos)), **guide_kw)
+            try:
+                compile_guide = getattr(st.engine, "compile_guide", None)
+                if compile_guide is None:
+                    raise ValueError("this backend does not serve guided decoding")
+                await asyncio.get_running_loop().run_in_executor(None, compile_guide, probe)
+            except ValueError as exc:
+                _leave()
+                return web.json_response({"error": str(exc)}, status=400)
         rid = request.headers.get("X-Request-ID") or data.get("request_id")
         request_id = str(rid) if rid else str(uuid.uuid4())[:8]
         span.set_attribute("app.request_id", request_id)
@@ -271,7 +289,7 @@ async def handle_chat(request: web.Request) -> web.Response:
 
         sp = SamplingParams(temperature=float(data.get("temperature", st.s.temperature)),
                             max_tokens=max(1, eff_new), ignore_eos=bool(data.get("ignore_eos", st.s.ignore_eos)),
-                            seed=data.get("seed"), logprobs=want_lp, **pen_kw)
+                            seed=data.get("seed"), logprobs=want_lp, **pen_kw, **guide_kw)
         queue_wait = 0.0
         final = None
         try:
@@ -311,6 +329,8 @@ async def handle_chat(request: web.Request) -> web.Response:
                     last_log = now
             if wait_span.is_recording():
                 wait_span.end()
+            if final is not None and final.finish_reason == "error":
+                raise RuntimeError("guided decoding: a sampled token left the guide")
             text = st.tok.decode(final.token_ids) if final is not None else ""
             el = time.monotonic() - t_sub
             ntok = len(final.token_ids) if final is not None else 0
@@ -374,6 +394,7 @@ async def handle_chat(request: web.Request) -> web.Response:
 
 
 PENALTY_KEYS = ("presence_penalty", "frequency_penalty", "repetition_penalty")
+GUIDE_KEYS = ("guided_regex", "guided_choice", "guided_json")
 
 
 def _penalty_fields(data: dict) -> dict:
@@ -491,6 +512,8 @@ def build_config(args):
         kw["speculative"] = "" if args.speculative in ("off", "none") else args.speculative
     if getattr(args, "num_speculative_tokens", None):
         kw["spec_tokens"] = args.num_speculative_tokens
+    if getattr(args, "guided_pool_states", None):
+        kw["guided_pool_states"] = args.guided_pool_states
     return EngineConfig.from_env(**kw)
 
 
@@ -590,6 +613,10 @@ def make_parser() -> argparse.ArgumentParser:
     p.add_argument("--speculative", choices=["ngram", "off"], default=None,
                    help="speculative decoding: n-gram (prompt lookup) drafts verified in one "
                         "decode step; outputs are those of plain decode (env LLM_SPECULATIVE)")
+    p.add_argument("--guided-pool-states", type=int, default=None,
+                   help="automaton states the guided-decoding pool holds for all live guides "
+                        "(default 4096: 1.05 GB at the Llama-3 vocabulary, allocated with the "
+                        "first guided request)")
     p.add_argument("--num-speculative-tokens", type=int, default=None,
                    help="drafts per sequence and step, at most 16 // GQA group - 1 "
                         "(default 3; env LLM_NUM_SPECULATIVE_TOKENS)")

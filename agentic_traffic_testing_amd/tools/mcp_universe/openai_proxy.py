@@ -14,6 +14,11 @@ Same contract as reference tools/mcp_universe/openai_proxy.py:43-165:
 * ``presence_penalty``, ``frequency_penalty``, ``logit_bias`` and vLLM's ``repetition_penalty``
   are forwarded as sent when present (the backend validates them; its 400 comes back as the
   502 above); requests without them are forwarded exactly as before;
+* vLLM's ``guided_regex``, ``guided_choice`` and ``guided_json`` are forwarded as sent when
+  present, and ``response_format: {"type": "json_schema", "json_schema": {"schema": S}}`` is
+  forwarded as ``guided_json: S``; ``{"type": "text"}``, ``{"type": "json_object"}`` (recursive
+  JSON is not a regular language: out of scope) and requests without these keys are forwarded
+  exactly as before;
 * ``GET /health`` and ``/ready`` report the backend URL; default port 8110.
 
 Deliberate fix (SURVEY §2.1 T5 notes the reference always returns null usage): when the
@@ -42,6 +47,7 @@ BACKEND_KEY = web.AppKey("backend_url", str)
 SESSION_KEY = web.AppKey("session", aiohttp.ClientSession)
 # forwarded to the backend as sent when present (repetition_penalty: vLLM's extension)
 PENALTY_KEYS = ("presence_penalty", "frequency_penalty", "repetition_penalty", "logit_bias")
+GUIDE_KEYS = ("guided_regex", "guided_choice", "guided_json")   # vLLM's extensions
 
 
 def flatten_messages(messages: t.Sequence[dict]) -> str:
@@ -130,9 +136,16 @@ async def handle_chat_completions(request: web.Request) -> web.Response:
         body["logprobs"] = k if isinstance(k, int) and not isinstance(k, bool) and k > 0 else 0
     # OpenAI's penalties and logit_bias (and vLLM's repetition_penalty extension) go to the
     # backend as sent - it validates them and answers 400; absent keys add nothing
-    for key in PENALTY_KEYS:
+    for key in PENALTY_KEYS + GUIDE_KEYS:
         if payload.get(key) is not None:
             body[key] = payload[key]
+    # OpenAI's structured output: the schema of a json_schema response format is the guide
+    # (an explicit guided_json wins); the backend validates it
+    rf = payload.get("response_format")
+    if isinstance(rf, dict) and rf.get("type") == "json_schema" and "guided_json" not in body:
+        js = rf.get("json_schema")
+        if isinstance(js, dict) and js.get("schema") is not None:
+            body["guided_json"] = js["schema"]
     url = request.app[BACKEND_KEY]
     try:
         async with request.app[SESSION_KEY].post(url, json=body) as resp:
