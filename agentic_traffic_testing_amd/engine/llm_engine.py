@@ -44,6 +44,12 @@ class RequestOutput:
     # [(token id, logprob), ...] alternatives, most likely first (empty lists for logprobs=0)
     logprobs: list | None = None
     top_logprobs: list | None = None
+    # SamplingParams.prompt_logprobs set: one entry per prompt token - None for the first, then
+    # log p(prompt[i] | prompt[:i]) - and None, then each position's [(token id, logprob), ...]
+    # alternatives (empty lists for prompt_logprobs=0).  Complete once the prompt is prefilled,
+    # i.e. in every output that carries a token.
+    prompt_logprobs: list | None = None
+    prompt_top_logprobs: list | None = None
 
     @property
     def completion_tokens(self) -> int:
@@ -174,6 +180,9 @@ class LLMEngine:
             # the automaton states live in one process's device memory, as the counts do
             raise ValueError("guided_regex, guided_choice and guided_json are not served by a "
                              "tensor-parallel engine")
+        if sampling.prompt_logprobs is not None and self.runner.tp_size > 1:
+            # the step message carries no score fields and the shards have no merge
+            raise ValueError("prompt_logprobs is not served by a tensor-parallel engine")
 
     def compile_guide(self, sampling: SamplingParams) -> Guide | None:
         """The compiled guide of ``sampling`` (None without one), from the cache or compiled
@@ -197,6 +206,9 @@ class LLMEngine:
         if sampling.penalised:
             with self.lock:  # device state on first need - here, never inside a graph capture
                 self.runner.ensure_penalty_state()
+        if sampling.prompt_logprobs is not None:
+            with self.lock:  # the scoring workspace likewise
+                self.runner.ensure_score_state()
         ids = list(map(int, prompt_ids))
         if not ids:
             ids = [self.tokenizer.bos_token_id]
@@ -355,6 +367,16 @@ class LLMEngine:
         self.timing["post"] += time.perf_counter() - now
         return outs
 
+    def _record_prompt_logprobs(self) -> None:
+        """Store the last executed step's prompt logprobs with their sequences (each entry
+        once, in position order: ``Sequence.set_prompt_logprob``)."""
+        res = self.runner.last_prompt_logprobs
+        if res is None:
+            return
+        lp, ids, vals = res
+        for k, (seq, idx, _) in enumerate(self.runner.last_scored):
+            seq.set_prompt_logprob(idx, lp[k], ((), ()) if ids is None else (ids[k], vals[k]))
+
     @staticmethod
     def _record_logprob(seq: Sequence, idx: int, lps, row: int) -> None:
         """Store row ``row`` of a step's logprob arrays as output token ``idx`` of a sequence
@@ -377,6 +399,7 @@ class LLMEngine:
         with self.lock:
             toks = self.runner.execute(batch)
             lps = self.runner.last_logprobs
+            self._record_prompt_logprobs()
             now = time.perf_counter()
             self.timing["execute"] += now - t0
             self.timing["steps"] += 1
@@ -425,6 +448,8 @@ class LLMEngine:
             return None  # a verify row's counts would depend on which drafts are accepted
         if r._guided(batch):
             return None  # a verify row's automaton state would depend on the rows before it
+        if any(seq.scoring for seq in batch.seqs):
+            return None  # a one-token chunk of a prompt that is being scored
         max_kv = r.verify_max_kv(S)
         if any(seq.num_tokens > max_kv for seq in batch.seqs):
             return None
@@ -507,7 +532,11 @@ class LLMEngine:
             finish_time=seq.finish_time, new_token_ids=list(new),
             logprobs=None if seq.logprobs is None else list(seq.logprobs[:len(ids)]),
             top_logprobs=(None if seq.top_logprobs is None
-                          else list(seq.top_logprobs[:len(ids)])))
+                          else list(seq.top_logprobs[:len(ids)])),
+            prompt_logprobs=(None if seq.prompt_logprobs is None
+                             else list(seq.prompt_logprobs)),
+            prompt_top_logprobs=(None if seq.prompt_top_logprobs is None
+                                 else list(seq.prompt_top_logprobs)))
 
     # ------------------------------------------------------------------------------------
     def generate(self, prompts, sampling: SamplingParams | list) -> list[RequestOutput]:

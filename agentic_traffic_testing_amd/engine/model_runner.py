@@ -45,16 +45,19 @@ class MetaLayout:
     """int32-word layout of the packed per-step metadata buffer."""
 
     def __init__(self, T: int, S: int, W: int, NT: int, R: int | None = None,
-                 penalty: bool = False, guide: bool = False):
+                 penalty: bool = False, guide: bool = False, score: int = 0):
         # R: rows the sampler runs over - one per sequence, or every row of a verify step
         # (speculative decoding), whose sampling fields are row-sized
         # penalty: a step of a penalty variant (V_PENALTY) carries four more per-row fields
         # behind the others; every other step's layout is what it was without them
         # guide: a step of a guide variant (V_GUIDE) carries one more per-row field behind those
+        # score: rows a scoring step (V_SCORE) scores - two more fields of that many entries
+        # behind those, present only in such a step
         R = S if R is None else R
         self.T, self.S, self.W, self.NT, self.R = T, S, W, NT, R
         self.penalty = bool(penalty)
         self.guide = bool(guide)
+        self.score = int(score)
         o = 0
         self.fields = {}
 
@@ -88,6 +91,12 @@ class MetaLayout:
             add("pen_pres", R, torch.float32)
         if guide:
             add("guide_slot", R)                # entry of the guide state; < 0: row unguided
+        if score:
+            # prompt logprobs: the step's rows to score and the token each one predicts - a
+            # field of its own, since a chunk's last row predicts the next prompt token, which
+            # is not among this step's input_ids
+            add("score_idx", score, torch.int64)
+            add("score_tgt", score)
         self.size = _even(o)
 
     def views(self, buf: torch.Tensor) -> dict:
@@ -124,17 +133,23 @@ OP_STEP, OP_CAPTURE, OP_STOP, OP_BARRIER = 1, 2, 3, 4
 # step's most demanding sequence; bit 3 - some sequence has a penalty or a logit bias (logits
 # materialised, penalised into an fp32 buffer before the sampler, token counts updated after);
 # bit 4 - some sequence is guided (logits materialised, masked into the fp32 buffer by its
-# automaton state before the sampler, the state advanced after)
+# automaton state before the sampler, the state advanced after); bit 5 - a prefill step some
+# of whose rows are scored for prompt logprobs (never a graph step: header word 7, a graph
+# step's bucket, then holds the number of scoring rows, plus SCORE_TOPN when some sequence
+# wants the alternatives too)
 V_TOPKP = 1
 V_PENALTY = 8
 V_GUIDE = 16
+V_SCORE = 32
+SCORE_TOPN = 1 << 30
 LP_NONE, LP_SAMPLED, LP_TOPN = 0, 1, 2   # no logprobs / the sampled token's / + the top-N
 TOP_N = ops.MAX_TOP_LOGPROBS             # a top-N step computes this many; requests cut theirs
 
 
-def variant_code(topkp: bool, lp_mode: int, penalty: bool = False, guide: bool = False) -> int:
+def variant_code(topkp: bool, lp_mode: int, penalty: bool = False, guide: bool = False,
+                 score: bool = False) -> int:
     return (int(bool(topkp)) | (lp_mode << 1) | (V_PENALTY if penalty else 0)
-            | (V_GUIDE if guide else 0))
+            | (V_GUIDE if guide else 0) | (V_SCORE if score else 0))
 
 
 def variant_lp(variant: int) -> int:
@@ -261,7 +276,7 @@ class ModelRunner:
         # metadata buffers (max layout)
         self.max_layout = MetaLayout(self.max_tokens, self.max_seqs, self.bt_width,
                                      self.max_tokens, max(self.max_seqs, self.ws_rows),
-                                     penalty=True, guide=True)
+                                     penalty=True, guide=True, score=self.max_tokens)
         pin = self.is_cuda
         # two pinned metadata buffers, used alternately: a step's H2D copy may still be queued
         # while the host packs the next step (async look-ahead decode, TP workers); an event
@@ -285,6 +300,16 @@ class ModelRunner:
         # logprob arrays of the last execute() / verify()-free step: None, or (lp [n],
         # top ids [n, TOP_N] | None, top logprobs [n, TOP_N] | None) as numpy
         self.last_logprobs = None
+        # prompt logprobs of the last execute() (SamplingParams.prompt_logprobs): None, or
+        # (lp [rows], top ids [rows, TOP_N] | None, top logprobs | None) as numpy, one row per
+        # entry of the step's ``score_rows_of`` list, in its order
+        self.last_prompt_logprobs = None
+        self.last_scored: list = []   # that step's ``score_rows_of`` list
+        # the fused scorer's record workspace, allocated with the first scoring request
+        # (ensure_score_state); None for an engine that saw none
+        self.score_ws: dict | None = None
+        self.score_fused = True  # False: every chunk materialises its logits (bench/scoring.py)
+        self._score_dev = None   # (lp, top ids, top logprobs) of the step in flight
         # the prefill GEMM's error word as of the last prefill step (0: every wait succeeded)
         self._err_host = torch.zeros(1, dtype=torch.int32, pin_memory=pin)
         # OR of the words read since the last take_kernel_error() (the device word is cleared
@@ -357,6 +382,39 @@ class ModelRunner:
         self._guide_pool: "collections.OrderedDict[tuple, dict]" = collections.OrderedDict()
         self._guide_of: dict[int, tuple] = {}     # seq_id -> key of the guide it holds
         self._f32_logits: torch.Tensor | None = None
+
+    # -- prompt logprobs ---------------------------------------------------------------------
+    def ensure_score_state(self) -> None:
+        """Allocate the fused scorer's workspace on first need - never inside a graph capture
+        (the engine calls this when a scoring request is added), never for an engine without
+        one: 16 B per (row, 16-column tile) of one ``LlamaModel.score_rows`` chunk."""
+        if self.score_ws is not None:
+            return
+        m = self.model
+        if not m.score_fusable(1):  # the CPU, TP shards: every chunk materialises its logits
+            self.score_ws = {}
+            return
+        n = 4 * m.score_chunk_rows() * (self.mcfg.vocab_size // 16)
+        print(f"[atta] prompt logprobs: scoring workspace {4 * n / 1e6:.1f} MB "
+              f"({m.score_chunk_rows()} rows x {self.mcfg.vocab_size // 16} tiles x 16 B)",
+              flush=True)
+        self.score_ws = {"rec": torch.zeros(n, dtype=torch.float32, device=self.device)}
+
+    @staticmethod
+    def score_rows_of(batch: Batch) -> list:
+        """The rows of a step that are scored: (sequence, prompt index it yields, row of the
+        step).  The row at position p of a sequence that still owes prompt logprobs predicts
+        prompt token p + 1; rows whose entry is already recorded (a prefill restarted after a
+        preemption) and the last prompt row (it predicts the first generated token:
+        ``logprobs``' business) are not scored."""
+        out, row = [], 0
+        for seq, s0, n in zip(batch.seqs, batch.q_start, batch.q_len):
+            if seq.scoring:
+                lo = max(s0 + 1, len(seq.prompt_logprobs))
+                hi = min(s0 + n + 1, seq.num_prompt)
+                out.extend((seq, i, row + i - 1 - s0) for i in range(lo, hi))
+            row += n
+        return out
 
     # -- sampling penalties ------------------------------------------------------------------
     def ensure_penalty_state(self) -> None:
@@ -645,7 +703,9 @@ class ModelRunner:
         NT = d["tile_seq"].shape[0]
         penalty = self._penalised(batch)
         guide = self._guided(batch)
-        lay = MetaLayout(T, S, self.bt_width, NT, penalty=penalty, guide=guide)
+        scored = self.last_scored = self.score_rows_of(batch)
+        lay = MetaLayout(T, S, self.bt_width, NT, penalty=penalty, guide=guide,
+                         score=len(scored))
         input_ids = np.zeros(T, dtype=np.int32)
         row = 0
         temps = np.zeros(S, dtype=np.float32)
@@ -689,6 +749,13 @@ class ModelRunner:
                 if seq.guide is not None and s0 + n == seq.num_tokens:
                     slot[i] = self._guide_slot(seq)
             arrays.update(guide_slot=slot)
+        if scored:
+            self.ensure_score_state()
+            arrays.update(
+                score_idx=np.fromiter((r for _, _, r in scored), dtype=np.int64,
+                                      count=len(scored)),
+                score_tgt=np.fromiter((s.prompt_ids[i] for s, i, _ in scored), dtype=np.int32,
+                                      count=len(scored)))
         return lay, arrays
 
     @property
@@ -739,13 +806,17 @@ class ModelRunner:
         logprob variant materialises the logits for ``ops.token_logprobs``."""
         return variant == variant_code(False, LP_SAMPLED) and self.tp_size == 1
 
-    def _forward_sample(self, v: dict, md: AttnMeta, num_parts: int, variant: int = 0):
+    def _forward_sample(self, v: dict, md: AttnMeta, num_parts: int, variant: int = 0,
+                        score_top: int = 0):
         """One step's forward + sampling.  ``variant`` (variant_code): bit 0 - some row uses
         top-p / top-k (logits are materialised and the top-k / top-p kernel samples every
         row); bits 1-2 - the step's logprob mode, whose results land in ws["lp"] (and
         ws["top_ids"] / ws["top_lp"]), one row per sampled row; bit 3 - some sequence is
         penalised (logits materialised, ``LlamaModel.sample_logits``' penalty tail); bit 4 - some
-        sequence is guided (logits materialised, its guide tail)."""
+        sequence is guided (logits materialised, its guide tail); bit 5 - the rows
+        v["score_idx"] are scored against v["score_tgt"] (``LlamaModel.score_rows`` with
+        ``score_top`` alternatives) in launches of their own after the sampler's; the sampled
+        rows see exactly what they see without it."""
         m = self.model
         T = v["input_ids"].shape[0]
         special = bool(variant & V_TOPKP)
@@ -769,7 +840,8 @@ class ModelRunner:
                or (lp_mode != LP_NONE and not lp_fused))
         # alternatives a materialised logprob step computes (None: no logprobs)
         lp_top = None if lp_mode == LP_NONE else (TOP_N if lp_mode == LP_TOPN else 0)
-        if (self.fused_decode and md.num_tiles == 0
+        score = bool(variant & V_SCORE)
+        if (self.fused_decode and md.num_tiles == 0 and not score
                 and md.num_decode == T and m.decode_step_fusable(T)):
             ws = self._ws_for(T)
             # grid over this step's partition bucket only (num_parts covers every row, in
@@ -786,7 +858,24 @@ class ModelRunner:
                          self.part_lse, num_parts, self.part_tokens,
                          prev_tokens=self.ws["tokens"] if decode_only else None,
                          feed_prev=v["feed_prev"] if decode_only else None,
-                         rows=v["logits_idx"])
+                         rows=(torch.cat([v["logits_idx"], v["score_idx"]]) if score
+                               else v["logits_idx"]))
+        if score:
+            # one gather and one final norm for both kinds of row: the first rows go to the
+            # sampler as ever, the rest are scored
+            n_s = v["logits_idx"].shape[0]
+            last, scored = last[:n_s], last[n_s:]
+            toks = self._sample_last(last, v, mat, special, pen, gd, lp_top, lp_fused,
+                                     decode_only)
+            self._score_dev = m.score_rows(scored, v["score_tgt"], score_top,
+                                           self.score_ws or None, fused=self.score_fused)
+            return toks
+        return self._sample_last(last, v, mat, special, pen, gd, lp_top, lp_fused, decode_only)
+
+    def _sample_last(self, last, v: dict, mat: bool, special: bool, pen, gd, lp_top, lp_fused,
+                     decode_only: bool):
+        """The sampler over a step's normalised last-token rows (``_forward_sample``)."""
+        m = self.model
         if not mat and m.sampler_fusable(last.shape[0]) and last.shape[0] <= self.max_seqs:
             # fused LM head + Gumbel-max sampler on the (already normalised) last rows
             return m.sample_rows(last, 0.0, v["temperature"], v["seeds"], v["steps"], self.ws,
@@ -823,6 +912,8 @@ class ModelRunner:
                 and self.graph_sizes and n <= self.graph_sizes[-1]):
             return 0
         b = next(b for b in self.graph_sizes if b >= n)
+        if any(s.scoring for s in batch.seqs) and self.score_rows_of(batch):
+            return 0  # (a one-token chunk of a prompt that is being scored)
         return b if self._graph_ok(b, self._variant(batch)) else 0
 
     @staticmethod
@@ -861,6 +952,13 @@ class ModelRunner:
             return lp, None, None
         return lp, self.ws["top_ids"][:n].cpu().numpy(), self.ws["top_lp"][:n].cpu().numpy()
 
+    def _fetch_prompt_logprobs(self):
+        """Synchronous copy of a scoring step's arrays, after the tokens' (None: no scoring)."""
+        dev, self._score_dev = self._score_dev, None
+        if dev is None:
+            return None
+        return tuple(None if t is None else t.cpu().numpy() for t in dev)
+
     def execute(self, batch: Batch) -> np.ndarray:
         """Run one step; returns sampled token ids (one per sequence in batch order).  A
         step in which a sequence asked for logprobs leaves them in ``last_logprobs``."""
@@ -870,10 +968,16 @@ class ModelRunner:
             h = self.launch(batch)
             toks = self.collect(h)
             self.last_logprobs = self.collect_logprobs(h)
+            self.last_prompt_logprobs = None
             return toks
         self.steps += 1
         variant = self._variant(batch)
         lay, arrays = self._prepare(batch)
+        score_word = 0
+        if lay.score:
+            variant |= V_SCORE
+            topn = any(s.sampling.prompt_logprobs for s in batch.seqs if s.scoring)
+            score_word = lay.score | (SCORE_TOPN if topn else 0)
         max_kv = int(arrays["seq_kvlen"][:batch.num_decode].max()) if batch.num_decode else 0
         if batch.num_decode == n and lay.NT == 0:
             # decode-only: in the partition size of this batch size (>= the 256-token count
@@ -883,7 +987,7 @@ class ModelRunner:
             num_parts = max(1, math.ceil(max_kv / self.part_tokens))
         host = self._pack(lay, arrays)
         hdr = np.array([OP_STEP, lay.T, lay.S, lay.W, lay.NT, batch.num_decode, num_parts,
-                        0, variant, n, lay.size, 0], dtype=np.int32)
+                        score_word, variant, n, lay.size, 0], dtype=np.int32)
         if self.publisher is not None:
             self.publisher.publish(np.concatenate([hdr, host]))
         toks = self._run(hdr)
@@ -895,6 +999,7 @@ class ModelRunner:
             ops.prefill_gemm_error_to(self._err_host, clear=True)
         out = toks[:n].cpu().numpy()
         self.last_logprobs = self._fetch_logprobs(variant, n)
+        self.last_prompt_logprobs = self._fetch_prompt_logprobs()
         word = int(self._err_host[0]) if self.is_cuda else 0
         if word:
             self._err_host.zero_()
@@ -1019,6 +1124,8 @@ class ModelRunner:
         """Decode-only batches can be launched asynchronously (every sampler runs on the
         device and leaves its tokens in ws["tokens"])."""
         n = len(batch.seqs)
+        if any(s.scoring for s in batch.seqs) and self.score_rows_of(batch):
+            return False  # a scoring step runs through execute(), which fetches its results
         return 0 < n <= self.max_seqs and batch.num_decode == n
 
     def launch(self, batch: Batch, lookahead: bool = False) -> dict:
@@ -1106,6 +1213,10 @@ class ModelRunner:
             v = lay.views(dev)
             return self._forward_verify(v, self._meta(v, num_decode, NT), num_parts,
                                         int(hdr[11]) & 0xFF, int(hdr[11]) >> 8)
+        n_score = score_top = 0
+        if variant & V_SCORE:  # never a graph step: word 7 is the scoring row count
+            n_score, score_top = bucket & (SCORE_TOPN - 1), (TOP_N if bucket & SCORE_TOPN else 0)
+            bucket = 0
         if bucket:
             key = (bucket, num_parts, variant)
             io = self.graph_io[key]
@@ -1114,13 +1225,13 @@ class ModelRunner:
             self.graph_steps += 1
             return io["out"]
         lay = MetaLayout(T, S, W, NT, penalty=bool(variant & V_PENALTY),
-                         guide=bool(variant & V_GUIDE))
+                         guide=bool(variant & V_GUIDE), score=n_score)
         dev = self.meta_dev[:size]
         self._h2d(dev, size)
         v = lay.views(dev)
         md = self._meta(v, num_decode, NT)
         # every rank samples (deterministic kernels over all-gathered logits under TP)
-        out = self._forward_sample(v, md, num_parts, variant)
+        out = self._forward_sample(v, md, num_parts, variant, score_top)
         if NT == 0 and num_decode == T and out is not None:
             # every rank keeps the decode samples where a look-ahead step embeds them from
             dev_toks = self.ws["tokens"]

@@ -138,7 +138,13 @@ class Scheduler:
         while self.waiting and budget > 0 and len(self.running) < self.max_num_seqs:
             seq = self.waiting[0]
             reserve = min(seq.num_tokens + 1, self.max_model_len)
-            cached = self.bm.allocate(seq.seq_id, seq.token_array(), reserve)
+            # a sequence that still owes prompt logprobs takes fresh blocks only: a cached
+            # position would have no hidden state to score
+            if seq.scoring:
+                cached = self.bm.allocate(seq.seq_id, seq.token_array(), reserve,
+                                          use_prefix=False)
+            else:
+                cached = self.bm.allocate(seq.seq_id, seq.token_array(), reserve)
             if cached < 0:
                 break  # KV pool full: wait for running sequences to finish
             self.waiting.popleft()

@@ -32,6 +32,12 @@ class SamplingParams:
     # rounded to the model dtype, before temperature, Gumbel noise and top-k / top-p (vLLM's
     # default "raw_logprobs").  Tokens do not depend on this field.
     logprobs: int | None = None
+    # None: no prompt logprobs; 0: log p(prompt[i] | prompt[:i]) for every prompt token but the
+    # first; N in 1 .. 20: also the N most likely tokens of each of those positions.  Defined as
+    # ``logprobs`` is (raw logits rounded to the model dtype, fp32 log-softmax).  A request that
+    # asks takes no prefix-cache hit until its prompt is scored: every position is computed.
+    # Tokens do not depend on this field.
+    prompt_logprobs: int | None = None
     # Penalties and bias (defaults: off).  For a sampled row, per token v, from the raw logit l
     # in fp32:  1. v occurs in the prompt or the tokens generated so far -> l = l / rep if l > 0
     # else l * rep;  2. c = times v was generated (the prompt does not count): l -= freq * c,
@@ -71,6 +77,11 @@ class SamplingParams:
                                or not 0 <= lp <= MAX_LOGPROBS):
             raise ValueError(f"logprobs must be None or an integer in 0 .. {MAX_LOGPROBS}, "
                              f"got {lp!r}")
+        lp = self.prompt_logprobs
+        if lp is not None and (isinstance(lp, bool) or not isinstance(lp, int)
+                               or not 0 <= lp <= MAX_LOGPROBS):
+            raise ValueError(f"prompt_logprobs must be None or an integer in 0 .. "
+                             f"{MAX_LOGPROBS}, got {lp!r}")
         for name in ("presence_penalty", "frequency_penalty"):
             v = getattr(self, name)
             if not _is_number(v) or not -2.0 <= v <= 2.0:
@@ -139,6 +150,11 @@ class Sequence:
     # (logprobs >= 1) the position's [(id, logprob), ...] alternatives
     logprobs: list | None = None
     top_logprobs: list | None = None
+    # with sampling.prompt_logprobs set: one entry per prompt token scored so far, in position
+    # order - entry 0 is None (nothing precedes the first token), entry i the logprob of
+    # prompt[i] given prompt[:i] and (prompt_logprobs >= 1) the position's alternatives
+    prompt_logprobs: list | None = None
+    prompt_top_logprobs: list | None = None
     # guided decoding: the compiled guide (engine/guided.py) and the host's shadow of the
     # automaton state - the table row after every token appended so far
     guide: object | None = None
@@ -175,6 +191,28 @@ class Sequence:
         if self.sampling.logprobs is not None:
             self.logprobs = []
             self.top_logprobs = []
+
+        if self.sampling.prompt_logprobs is not None:
+            self.prompt_logprobs = [None]
+            self.prompt_top_logprobs = [None]
+
+    @property
+    def scoring(self) -> bool:
+        """Does this sequence still owe prompt logprobs?  Until it does not, it is admitted
+        without the prefix cache, so that every prompt position has a hidden state."""
+        return self.prompt_logprobs is not None and len(self.prompt_logprobs) < self.num_prompt
+
+    def set_prompt_logprob(self, idx: int, lp: float, top) -> bool:
+        """Record prompt token ``idx``'s logprob and alternatives (as ``set_logprob``'s).
+        Entries are recorded once, in position order: any other ``idx`` is ignored (False)."""
+        if self.prompt_logprobs is None or idx != len(self.prompt_logprobs) \
+                or idx >= self.num_prompt:
+            return False
+        n = self.sampling.prompt_logprobs
+        alts = [(int(i), float(v)) for i, v in zip(top[0][:n], top[1][:n])] if n else []
+        self.prompt_logprobs.append(float(lp))
+        self.prompt_top_logprobs.append(alts)
+        return True
 
     def append(self, tok: int):
         self.output_ids.append(int(tok))

@@ -865,6 +865,56 @@ class LlamaModel:
         self.tp_group.all_reduce_max(keys, tokens=toks)  # IPC: one kernel, tokens included
         return toks
 
+    def score_chunk_rows(self) -> int:
+        """Rows per launch of ``score_rows``: what the wide kernel takes over a pre-shuffled
+        LM head, else what the 16-row-tile GEMV takes."""
+        return ops.WIDE_ROWS if self.lm_head_ps is not None else ops.SKINNY_ROWS
+
+    def score_fusable(self, rows: int) -> bool:
+        """Can the fused LM head score these rows (``ops.lm_head_score``)?  One GPU, and the
+        LM-head kernels with the scoring epilogue, as ``sampler_fusable``."""
+        lm_ps = self.lm_head_ps is not None
+        return (self.tp_size == 1 and self.device.type == "cuda"
+                and self.cfg.hidden_size % 128 == 0
+                and ops.fused_kernel(rows, lm_ps, False, "score") is not None)
+
+    def score_rows(self, hidden: torch.Tensor, targets: torch.Tensor, n_top: int,
+                   ws: dict | None, fused: bool = True):
+        """Teacher-forced scoring: the logprob of token ``targets[r]`` (int32) under row r of
+        ``hidden`` (already normalised: eps = 0, as the rows ``forward(rows=...)`` returns),
+        and with ``n_top`` >= 1 each row's ``n_top`` most likely tokens with theirs.  Returns
+        (lp [R] fp32, top_ids [R, n_top] int32 | None, top_lp [R, n_top] fp32 | None).
+
+        Chunks of at most ``score_chunk_rows`` rows.  ``n_top`` == 0 where the fused route
+        exists (``score_fusable``; ``fused=False`` turns it off): ``ops.lm_head_score`` per
+        chunk with ``ws["rec"]`` as its record workspace - each chunk streams the LM head once
+        and no logits reach memory.  Otherwise per chunk ``compute_logits`` and
+        ``ops.token_logprobs``: the logits buffer never exceeds one chunk."""
+        R = hidden.shape[0]
+        dev = hidden.device
+        lp = torch.empty(R, dtype=torch.float32, device=dev)
+        top_ids = top_lp = None
+        if n_top > 0:
+            top_ids = torch.empty(R, n_top, dtype=torch.int32, device=dev)
+            top_lp = torch.empty(R, n_top, dtype=torch.float32, device=dev)
+        lm_ps = self.lm_head_ps is not None
+        step = self.score_chunk_rows()
+        tok64 = targets.long() if R else targets
+        for r0 in range(0, R, step):
+            r1 = min(R, r0 + step)
+            chunk = hidden[r0:r1]
+            if n_top == 0 and fused and ws is not None and self.score_fusable(r1 - r0):
+                ops.lm_head_score(chunk, self.lm_head_ps if lm_ps else self.lm_head, 0.0,
+                                  targets[r0:r1], ws["rec"], out=lp[r0:r1], preshuffled=lm_ps)
+                continue
+            logits = self.compute_logits(chunk)
+            got = ops.token_logprobs(logits, tok64[r0:r1], n_top)
+            lp[r0:r1].copy_(got[0])
+            if n_top > 0:
+                top_ids[r0:r1].copy_(got[1])
+                top_lp[r0:r1].copy_(got[2])
+        return lp, top_ids, top_lp
+
     def compute_logits(self, hidden: torch.Tensor) -> torch.Tensor:
         logits = ops.linear(hidden, self.lm_head)
         if self.tp_size > 1:

@@ -413,9 +413,9 @@ def _policy_tops() -> tuple[int, int, int]:
 def fused_kernel(m: int, preshuffled: bool, fp8: bool = False, epi: str = "plain",
                  mxfp4: bool = False, wide_w4: bool = False) -> str | None:
     """Which hand-written weight-streaming kernel runs ``m`` rows over this weight layout with
-    this epilogue ("plain" | "resadd" | "qkv" | "silu" | "sample" | "sample_lp" | "push";
-    "sample_lp", the sampler with the logprob record, routes as "sample" does but has no fp8
-    build): "skinny" (the
+    this epilogue ("plain" | "resadd" | "qkv" | "silu" | "sample" | "sample_lp" | "score" |
+    "push"; "sample_lp", the sampler with the logprob record, and "score", the teacher-forced
+    scorer, route as "sample" does but have no fp8 build): "skinny" (the
     16-row-tile GEMV), "wide", "midm", or None (no kernel: the native call would fail).  The
     routing table of csrc/gemv.hip ``route()`` (written out there and in docs/kernels.md)
     under the policy limits above.  ``mxfp4``: the 4-bit copies (``preshuffle_mxfp4``), which
@@ -424,9 +424,9 @@ def fused_kernel(m: int, preshuffled: bool, fp8: bool = False, epi: str = "plain
     ``decode_qkv_rope`` / ``decode_gate_up_silu``).  Pure: no native call, usable without a
     GPU."""
     skinny_top, wide_top, midm_top = _policy_tops()
-    if m < 1 or (epi == "sample_lp" and fp8):
+    if m < 1 or (epi in ("sample_lp", "score") and fp8):
         return None
-    if epi == "sample_lp":
+    if epi in ("sample_lp", "score"):
         epi = "sample"
     if mxfp4:
         if epi in ("sample", "push"):
@@ -1278,6 +1278,40 @@ def decode_lm_head_sample(x, w, eps, temperature, seeds, steps, keys, tokens=Non
                                    vocab_offset, decode_waves("lm_head", preshuffled),
                                    preshuffled)
     return tokens
+
+
+def lm_head_score(x, w, eps, targets, ws, out=None, preshuffled=False):
+    """Teacher-forced scoring in the fused LM head, no logits materialised: lp[m] = the logprob
+    of token ``targets[m]`` (int32, inside the vocabulary: the caller's contract) in row m,
+    ``l_tok - logsumexp(l)`` in fp32 over the LM-head product rounded to the model dtype, as a
+    sampled token's logprob is defined (``eps`` > 0: the final RMSNorm first, its weight folded
+    into ``w``).  The SCORE epilogue and its finalize (csrc/skinny.h): at most 128 rows over
+    pre-shuffled weights, else 32; 16-bit weights; one GPU.  ``ws``: fp32 scratch of 4 words
+    per (row, 16-column tile), i.e. ``M * vocab / 4`` floats.  Returns fp32 [M] (``out``'s
+    first M entries when given)."""
+    _need_cuda(x, preshuffled)
+    m = x.shape[0]
+    if targets.dtype != torch.int32 or targets.numel() < m:
+        raise ValueError("lm_head_score: targets must be int32 with one id per row")
+    if not x.is_cuda:
+        lp = ref.lm_head_score(x, w, eps, targets[:m])
+        if out is None:
+            return lp
+        out[:m].copy_(lp)
+        return out[:m]
+    kernel = fused_kernel(m, preshuffled, False, "score")
+    if kernel is None:
+        raise ValueError(f"lm_head_score: no fused kernel for {m} rows "
+                         f"({'pre-shuffled' if preshuffled else 'row-major'} weights)")
+    if ws is None:
+        raise ValueError("lm_head_score: needs the ws workspace")
+    if out is None:
+        out = torch.empty(m, dtype=torch.float32, device=x.device)
+    if kernel == "wide":  # its planner may split K
+        ensure_splitk_workspace(x.device)
+    _native().fused_lm_head_score(out, ws, x, w, eps, targets,
+                                  decode_waves("lm_head", preshuffled), preshuffled)
+    return out[:m]
 
 
 def key_to_token(keys: torch.Tensor) -> torch.Tensor:

@@ -929,6 +929,34 @@ void fused_lm_head_sample_lp(at::Tensor tokens, at::Tensor lp, at::Tensor keys, 
            "fused_lm_head_sample_lp");
 }
 
+// Teacher-forced scoring in the fused LM head: lp[m] = logprob of targets[m] (int32, the
+// caller keeps them inside the vocabulary) in row m.  ws: fp32 scratch of 4 words per (row,
+// 16-column tile).  No sampler, no keys.
+void fused_lm_head_score(at::Tensor lp, at::Tensor ws, const at::Tensor& x, const at::Tensor& w,
+                         double eps, const at::Tensor& targets, int64_t waves, bool preshuffled) {
+  check_skinny(x, w, "fused_lm_head_score");
+  TORCH_CHECK(x.scalar_type() == w.scalar_type(), "fused_lm_head_score: 16-bit weights");
+  TORCH_CHECK(lp.scalar_type() == at::kFloat && ws.scalar_type() == at::kFloat &&
+                  targets.scalar_type() == at::kInt,
+              "fused_lm_head_score: dtypes (lp, ws fp32; targets int32)");
+  const int64_t M = x.size(0), slots = M * (w.size(0) / 16);
+  TORCH_CHECK(w.size(0) % 16 == 0 && lp.numel() >= M && targets.numel() >= M &&
+                  lp.is_contiguous() && targets.is_contiguous(),
+              "fused_lm_head_score: vocab % 16 == 0, lp and targets need M contiguous entries");
+  TORCH_CHECK(ws.numel() >= 4 * slots && ws.is_contiguous() &&
+                  reinterpret_cast<uintptr_t>(ws.data_ptr()) % 16 == 0,
+              "fused_lm_head_score: ws needs 4 * M * (vocab / 16) floats, 16-B aligned");
+  TORCH_CHECK(ws.device() == x.device() && lp.device() == x.device() &&
+                  targets.device() == x.device(),
+              "fused_lm_head_score: one device");
+  const at::DeviceGuard g(x.device());
+  check_rc(atta_fused_lm_head_score(lp.data_ptr<float>(), ws.data_ptr(), x.data_ptr(),
+                                    w.data_ptr(), targets.data_ptr<int>(), M, w.size(0),
+                                    x.size(1), x.stride(0), static_cast<float>(eps), waves,
+                                    skinny_dtype(x, preshuffled), cur_stream()),
+           "fused_lm_head_score");
+}
+
 // Row-wise fp8 activation quantisation fused into norm / SiLU-mul / plain rows.
 void quant_rows_fp8(at::Tensor q, at::Tensor scale, const at::Tensor& x,
                     const c10::optional<at::Tensor>& w, int64_t mode, double eps,
@@ -1337,6 +1365,9 @@ TORCH_LIBRARY(atta, m) {
       "fused_lm_head_sample_lp(Tensor(a!) tokens, Tensor(b!) lp, Tensor(c!) keys, "
       "Tensor(d!) lp_ws, Tensor x, Tensor w, float eps, Tensor temperature, Tensor seeds, "
       "Tensor steps, int waves, bool preshuffled=False) -> ()");
+  m.def(
+      "fused_lm_head_score(Tensor(a!) lp, Tensor(b!) ws, Tensor x, Tensor w, float eps, "
+      "Tensor targets, int waves, bool preshuffled=False) -> ()");
   m.def("sample_finalize(Tensor(a!) tokens, Tensor keys, int n_tiles) -> ()");
   m.def("skinny_gemm(Tensor(a!) y, Tensor x, Tensor w, Tensor? residual, int waves, "
         "bool preshuffled=False, Tensor? w_scale=None, int ksplit=1, "
@@ -1424,6 +1455,7 @@ TORCH_LIBRARY_IMPL(atta, CUDA, m) {
   m.impl("gemm_w4a8", &gemm_w4a8);
   m.impl("fused_lm_head_sample", &fused_lm_head_sample);
   m.impl("fused_lm_head_sample_lp", &fused_lm_head_sample_lp);
+  m.impl("fused_lm_head_score", &fused_lm_head_score);
   m.impl("sample_finalize", &sample_finalize);
   m.impl("set_splitk_workspace", &set_splitk_workspace);
   m.impl("quant_rows_fp8", &quant_rows_fp8);

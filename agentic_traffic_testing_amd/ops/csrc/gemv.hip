@@ -93,8 +93,8 @@ static void launch_t(int dtype, dim3 grid, hipStream_t st, const SkinnyParams& p
   constexpr std::false_type no{};
   auto by_layout = [&](auto t, auto nt_) {
     if (w8) {
-      // (no fp8 build of the logprob sampler epilogue: route() sends none here)
-      if constexpr (EPI != EPI_SAMPLE_LP) launch(t, nt_, yes, yes);
+      // (no fp8 build of the logprob sampler and scorer epilogues: route() sends none here)
+      if constexpr (!epi_records(EPI)) launch(t, nt_, yes, yes);
     } else if (ps) launch(t, nt_, yes, no);
     else launch(t, nt_, no, no);
   };
@@ -260,6 +260,52 @@ __global__ void __launch_bounds__(kFinThreads) sample_lp_finalize_kernel(
     }
   }
 }
+
+// The SCORE epilogue's finalize, one workgroup per row: sample_lp_finalize_kernel's load shape
+// and lse_merge tree over the records rec[m][tile] = {max_i, s_i, target's raw logit or 0},
+// without the keys:  lp[m] = rec[m][target >> 4].z - (gmax + log(sum_i s_i exp(max_i - gmax))).
+__global__ void __launch_bounds__(kFinThreads) score_finalize_kernel(
+    float* lp, const int* targets, const f32x4* rec, int n_tiles, int vocab_offset) {
+  __shared__ float rm[kFinThreads / kWave], rs[kFinThreads / kWave];
+  const int m = blockIdx.x;
+  const f32x4* rrow = rec + static_cast<int64_t>(m) * n_tiles;
+  float gm = -__builtin_huge_valf(), gs = 0.f;
+  for (int base = 0; base < n_tiles; base += 8 * kFinThreads) {
+    f32x4 r[8];
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int i = base + j * kFinThreads + threadIdx.x;
+      r[j] = i < n_tiles ? rrow[i] : f32x4{-__builtin_huge_valf(), 0.f, 0.f, 0.f};
+    }
+#pragma unroll
+    for (int j = 0; j < 8; ++j) lse_merge(gm, gs, r[j][0], r[j][1]);
+  }
+#pragma unroll
+  for (int o = 1; o < kWave; o <<= 1) {
+    const float om = __shfl_xor(gm, o, kWave), os = __shfl_xor(gs, o, kWave);
+    lse_merge(gm, gs, om, os);
+  }
+  if ((threadIdx.x & (kWave - 1)) == 0) {
+    rm[threadIdx.x / kWave] = gm;
+    rs[threadIdx.x / kWave] = gs;
+  }
+  __syncthreads();
+  if (threadIdx.x < kWave) {
+    const bool has = threadIdx.x < kFinThreads / kWave;
+    gm = has ? rm[threadIdx.x] : -__builtin_huge_valf();
+    gs = has ? rs[threadIdx.x] : 0.f;
+#pragma unroll
+    for (int o = 1; o < kWave; o <<= 1) {
+      const float om = __shfl_xor(gm, o, kWave), os = __shfl_xor(gs, o, kWave);
+      lse_merge(gm, gs, om, os);
+    }
+    if (threadIdx.x == 0) {
+      // the target's tile; clamped so that a bad id can never index past the row
+      const int tile = min(max((targets[m] - vocab_offset) >> 4, 0), n_tiles - 1);
+      lp[m] = rrow[tile][2] - (gm + logf(gs));
+    }
+  }
+}
 }  // namespace atta
 
 using namespace atta;
@@ -323,20 +369,20 @@ void atta_get_wide_min_rows(int* m, int* m_silu) {
 // wide_w4: the caller's explicit per-call choice (kWideW4 in the dtype code); a default MXFP4
 // call past 32 rows keeps having no kernel.
 // SAMPLE_LP (the sampler with the logprob record) routes as SAMPLE does, except that it has no
-// fp8 build at any row count: None.
+// fp8 build at any row count: None.  SCORE (the teacher-forced scorer) routes as SAMPLE_LP.
 enum class Route { None, Skinny, Wide, MidM };
 static Route route(int M, bool ps, bool w8, bool w4, int epi, bool wide_w4 = false) {
   if (M < 1) return Route::None;
   if (w4) {
-    if (epi_samples(epi)) return Route::None;
+    if (epi_lm_head(epi)) return Route::None;
     if (M <= kSkinnyMaxM) return Route::Skinny;
     return wide_w4 && M <= kWideMaxM ? Route::Wide : Route::None;
   }
-  if (epi == EPI_SAMPLE_LP && w8) return Route::None;
+  if (epi_records(epi) && w8) return Route::None;
   if (!ps) return M <= kSkinnyMaxM ? Route::Skinny : Route::None;
   const int wide_min = epi == EPI_SILU ? g_wide_min_m_silu : g_wide_min_m;
   if (M <= kSkinnyMaxM && (w8 || M < wide_min)) return Route::Skinny;
-  if (epi_samples(epi) && (w8 || M > kWideMaxM)) return Route::None;
+  if (epi_lm_head(epi) && (w8 || M > kWideMaxM)) return Route::None;
   if (M <= kWideMaxM) return Route::Wide;
   return M <= kMidmMaxM ? Route::MidM : Route::None;
 }
@@ -597,6 +643,26 @@ int atta_fused_lm_head_sample_lp(int64_t* tokens, float* lp, unsigned long long*
   if (const int rc = launch_routed<EPI_SAMPLE_LP>(p, N / 16, waves, 1, dtype, stream)) return rc;
   sample_lp_finalize_kernel<<<M, kFinThreads, 0, stream>>>(tokens, lp, keys, lp_records(p), N / 16,
                                                            0);
+  return static_cast<int>(hipGetLastError());
+}
+
+// Teacher-forced scoring: the SCORE epilogue and its finalize, lp[m] = logprob of targets[m] in
+// row m over the raw logits.  No sampler and no keys; ws: M * N / 16 records of 16 B.  One GPU
+// only: vocab_offset is 0.  A target outside [0, N) is the caller's error (its lp is then that
+// of a clamped tile's record, never a read past the row).
+int atta_fused_lm_head_score(float* lp, void* ws, const void* x, const void* w,
+                             const int* targets, int M, int N, int K, int64_t x_stride, float eps,
+                             int waves, int dtype, hipStream_t stream) {
+  const int ps = (dtype & kPreshuffled) ? 1 : 0;
+  dtype &= ~kPreshuffled;
+  if (N % 16 != 0 || lp == nullptr || ws == nullptr || targets == nullptr) return -1;
+  SkinnyParams p = base_params(x, w, M, N, K, x_stride, eps, ps, nullptr);
+  p.key_stride = N / 16;
+  p.vocab_offset = 0;
+  p.positions = targets;                // score_targets()
+  p.y = static_cast<uint16_t*>(ws);     // lp_records()
+  if (const int rc = launch_routed<EPI_SCORE>(p, N / 16, waves, 1, dtype, stream)) return rc;
+  score_finalize_kernel<<<M, kFinThreads, 0, stream>>>(lp, targets, lp_records(p), N / 16, 0);
   return static_cast<int>(hipGetLastError());
 }
 

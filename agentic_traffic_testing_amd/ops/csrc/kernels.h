@@ -149,6 +149,13 @@ int atta_fused_lm_head_sample_lp(int64_t* tokens, float* lp, unsigned long long*
                                  const int64_t* seeds, const int64_t* steps, int waves,
                                  int dtype, hipStream_t stream);
 
+// teacher-forced scoring (EPI_SCORE): lp[m] = logprob of targets[m] (int32 token id in [0, N))
+// in row m; ws: M * N / 16 records of 16 B (16-B aligned), 16-bit weights, one GPU.  M <= 128
+// over pre-shuffled weights, else <= 32.  -1 where atta_fused_lm_head_sample_lp returns it.
+int atta_fused_lm_head_score(float* lp, void* ws, const void* x, const void* w,
+                             const int* targets, int M, int N, int K, int64_t x_stride, float eps,
+                             int waves, int dtype, hipStream_t stream);
+
 int atta_sample_finalize(int64_t* tokens, const unsigned long long* keys, int M, int n_tiles,
                          hipStream_t stream);
 

@@ -24,11 +24,18 @@ enum Epi {
   // SAMPLE's keys, plus per (row, tile) the record the row's logprob is finished from
   // (gemv.hip sample_lp_finalize_kernel): the tile's log-sum-exp partial over its 16 raw
   // logits and the raw logit of its winning column
-  EPI_SAMPLE_LP = 5
+  EPI_SAMPLE_LP = 5,
+  // teacher-forced scoring, no sampler: per (row, tile) SAMPLE_LP's record with the raw logit
+  // of the row's TARGET column in place of the winner's (gemv.hip score_finalize_kernel)
+  EPI_SCORE = 6
 };
 
 // the LM-head sampler epilogues (unsplit, 16-bit weights only: route() in gemv.hip)
 constexpr bool epi_samples(int epi) { return epi == EPI_SAMPLE || epi == EPI_SAMPLE_LP; }
+// every LM-head epilogue: the samplers and the scorer route alike
+constexpr bool epi_lm_head(int epi) { return epi_samples(epi) || epi == EPI_SCORE; }
+// the LM-head epilogues with no fp8 build
+constexpr bool epi_records(int epi) { return epi == EPI_SAMPLE_LP || epi == EPI_SCORE; }
 
 template <typename T>
 struct MfmaK32;
@@ -77,14 +84,15 @@ __device__ __forceinline__ typename MfmaK32<T>::frag8 fp8x8_to_frag(uint32_t lo,
 struct SkinnyParams {
   const uint16_t* x;
   const uint16_t* w;
-  uint16_t* y;  // PLAIN / RESADD (in place) / SILU output / QKVROPE q output / SAMPLE_LP records
+  uint16_t* y;  // PLAIN / RESADD (in place) / SILU output / QKVROPE q output / SAMPLE_LP and
+                // SCORE records
   int64_t x_stride, y_stride;
   int M, N, K;
   float eps;  // > 0: fused RMSNorm (norm weight folded into W)
   // QKVROPE
   uint16_t* k_cache;
   uint16_t* v_cache;
-  const int* positions;
+  const int* positions;  // SCORE: the rows' target ids (score_targets)
   const int* slots;
   const float* cos_sin;
   int n_q_heads, n_kv_heads, bs_shift;
@@ -128,6 +136,12 @@ struct SkinnyParams {
 // it every other kernel's argument layout, stays as it is.
 __device__ __host__ __forceinline__ f32x4* lp_records(const SkinnyParams& p) {
   return reinterpret_cast<f32x4*>(p.y);
+}
+
+// SCORE keeps its records there too, {max, sum exp(l - max), target's raw logit or 0, 0}, and
+// its per-row int32 target ids behind the pointer of QKVROPE's positions, for the same reason.
+__device__ __host__ __forceinline__ const int* score_targets(const SkinnyParams& p) {
+  return p.positions;
 }
 
 __device__ __forceinline__ unsigned ordered_bits(float f) {
@@ -282,6 +296,29 @@ __device__ __forceinline__ void tile_epilogue(const SkinnyParams& p, const int t
         p.keys[at] = key;
         lp_records(p)[at] = f32x4{mx, sum, lwin, 0.f};
       }
+    }
+  } else if constexpr (EPI == EPI_SCORE) {
+    // SAMPLE_LP's record over the raw logits with the target's logit for the winner's: no
+    // keys, no temperature / seed / step loads, no noise
+    for (int e = tid; e < 16 * 16 * MTMAX; e += nthr) {
+      const int m = e >> 4, n = e & 15;
+      float raw = -__builtin_huge_valf();
+      int tc = -1;  // the target's column in this tile, if it has one
+      if (m < p.M) {
+        const float sc = norm ? inv_rms[m] : 1.f;
+        raw = to_f32<T>(from_f32<T>(red[m][n] * sc));  // bf16 logits, as F.linear
+        tc = score_targets(p)[m] - p.vocab_offset - tile * 16;
+      }
+      float mx = raw;
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) mx = fmaxf(mx, __shfl_xor(mx, o, kWave));
+      float sum = m < p.M ? __expf(raw - mx) : 0.f;
+#pragma unroll
+      for (int o = 1; o < 16; o <<= 1) sum += __shfl_xor(sum, o, kWave);
+      const float ltgt = __shfl(raw, tc & 15, 16);
+      if (n == 0 && m < p.M)
+        lp_records(p)[static_cast<int64_t>(m) * p.key_stride + tile] =
+            f32x4{mx, sum, (tc >= 0 && tc < 16) ? ltgt : 0.f, 0.f};
     }
   }
 }

@@ -61,7 +61,7 @@ struct EpiIn {
   int rows[RPL];
   bool ok[RPL];
   u32x4 res[RPL][2];  // RESADD: the residual row segment (16 values)
-  int slot[RPL];      // QKVROPE
+  int slot[RPL];      // QKVROPE; SCORE: the row's target id
   f32x4 cs[RPL][4];   // QKVROPE: cos d..d+7, sin d..d+7
   float temp[RPL];    // SAMPLE
   uint64_t seed[RPL], step[RPL];
@@ -113,6 +113,9 @@ __device__ __forceinline__ void epi_load(const SkinnyParams& p, const int tile, 
       in.seed[j] = static_cast<uint64_t>(p.seeds[m]);
       in.step[j] = static_cast<uint64_t>(p.steps[m]);
     }
+  } else if constexpr (EPI == EPI_SCORE) {
+#pragma unroll
+    for (int j = 0; j < RPL; ++j) in.slot[j] = score_targets(p)[in.ok[j] ? in.rows[j] : 0];
   }
 }
 
@@ -257,6 +260,27 @@ __device__ __forceinline__ void epi_apply(const SkinnyParams& p, const int tile,
       const int64_t at = static_cast<int64_t>(m) * p.key_stride + tile;
       p.keys[at] = best;
       lp_records(p)[at] = f32x4{mx, sum, lwin, 0.f};
+    }
+  } else if constexpr (EPI == EPI_SCORE) {
+    // SAMPLE_LP's record with the target's raw logit for the winner's, and no sampler
+    // (skinny.h, EPI_SCORE)
+#pragma unroll
+    for (int j = 0; j < RPL; ++j) {
+      if (!in.ok[j]) continue;
+      const int m = in.rows[j];
+      const float sc = norm ? inv_rms[m - rbase] : 1.f;
+      const int tc = in.slot[j] - p.vocab_offset - tile * 16;  // the target's column, if here
+      float raw[16], mx = -__builtin_huge_valf(), ltgt = 0.f;
+#pragma unroll
+      for (int n = 0; n < 16; ++n) {
+        raw[n] = to_f32<T>(from_f32<T>(red[m - rbase][n] * sc));  // bf16 logits, as F.linear
+        mx = fmaxf(mx, raw[n]);
+        ltgt = n == tc ? raw[n] : ltgt;
+      }
+      float sum = 0.f;
+#pragma unroll
+      for (int n = 0; n < 16; ++n) sum += __expf(raw[n] - mx);
+      lp_records(p)[static_cast<int64_t>(m) * p.key_stride + tile] = f32x4{mx, sum, ltgt, 0.f};
     }
   }
 }
@@ -777,6 +801,13 @@ inline int launch_epi(int epi, dim3 grid, hipStream_t st, const SkinnyParams& p,
         if constexpr (kNormOk) wide_kernel<T, WAVES, MT, EPI_SAMPLE_LP, true, TPW><<<grid, blk, 0, st>>>(p, ntiles);
       } else {
         wide_kernel<T, WAVES, MT, EPI_SAMPLE_LP, false, TPW><<<grid, blk, 0, st>>>(p, ntiles);
+      }
+      return 0;
+    case EPI_SCORE:
+      if (norm) {
+        if constexpr (kNormOk) wide_kernel<T, WAVES, MT, EPI_SCORE, true, TPW><<<grid, blk, 0, st>>>(p, ntiles);
+      } else {
+        wide_kernel<T, WAVES, MT, EPI_SCORE, false, TPW><<<grid, blk, 0, st>>>(p, ntiles);
       }
       return 0;
     default: return -1;

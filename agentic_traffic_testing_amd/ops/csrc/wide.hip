@@ -92,6 +92,10 @@ static int launch_reduce(int epi, const SkinnyParams& p, int ntiles, int S, int 
       if (norm) wide_reduce_kernel<T, MT, EPI_SAMPLE_LP, true><<<grid, blk, 0, st>>>(p, ntiles, S, waves);
       else wide_reduce_kernel<T, MT, EPI_SAMPLE_LP, false><<<grid, blk, 0, st>>>(p, ntiles, S, waves);
       return 0;
+    case EPI_SCORE:
+      if (norm) wide_reduce_kernel<T, MT, EPI_SCORE, true><<<grid, blk, 0, st>>>(p, ntiles, S, waves);
+      else wide_reduce_kernel<T, MT, EPI_SCORE, false><<<grid, blk, 0, st>>>(p, ntiles, S, waves);
+      return 0;
     default: return -1;
   }
 }

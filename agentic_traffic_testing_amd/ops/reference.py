@@ -297,6 +297,16 @@ def lm_head_sample_logprobs(x: torch.Tensor, w: torch.Tensor, eps: float, temper
     return toks, token_logprobs(logits, toks)[0]
 
 
+def lm_head_score(x: torch.Tensor, w: torch.Tensor, eps: float, targets: torch.Tensor):
+    """What the fused LM head with the scoring epilogue computes, and the definition of a
+    prompt logprob: the logprob of ``targets[m]`` in row m over the LM-head product rounded to
+    the model dtype (``eps`` > 0: the final RMSNorm first, its weight folded into ``w``)."""
+    if eps > 0:
+        x = rms_norm(x, torch.ones(x.shape[1], dtype=x.dtype, device=x.device), eps)
+    logits = torch.nn.functional.linear(x, w)
+    return token_logprobs(logits, targets, 0)[0]
+
+
 def _ordered_bits(v: float) -> int:
     import struct
 

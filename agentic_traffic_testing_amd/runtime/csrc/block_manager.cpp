@@ -89,8 +89,10 @@ class BlockManager {
 
   // Admit a new sequence.  Returns the number of prompt tokens served from the prefix
   // cache, or -1 if there are not enough blocks (nothing is changed in that case).
+  // use_prefix = false skips the lookup: the sequence takes fresh blocks only (every position
+  // is computed) and the query / hit counters stay as they are.
   int64_t allocate(int64_t seq_id, py::array_t<int64_t, py::array::c_style> tokens,
-                   int64_t reserve_tokens) {
+                   int64_t reserve_tokens, bool use_prefix = true) {
     if (seqs_.count(seq_id)) throw std::runtime_error("sequence already allocated");
     auto buf = tokens.unchecked<1>();
     const int64_t n = buf.shape(0);
@@ -99,7 +101,7 @@ class BlockManager {
     // -- prefix lookup
     std::vector<int32_t> hit_blocks;
     std::vector<uint64_t> hit_hashes;
-    if (prefix_caching_) {
+    if (prefix_caching_ && use_prefix) {
       const int64_t full = (n - 1) / block_size_;
       uint64_t h = 0;
       for (int64_t i = 0; i < full; ++i) {
@@ -116,8 +118,10 @@ class BlockManager {
       if (ref_[b] == 0) ++revive;
     const int fresh = total_blocks - static_cast<int>(hit_blocks.size());
     if (fresh > num_free_blocks() - revive) return -1;
-    queries_ += (n - 1) / block_size_;
-    hits_ += static_cast<int64_t>(hit_blocks.size());
+    if (use_prefix) {
+      queries_ += (n - 1) / block_size_;
+      hits_ += static_cast<int64_t>(hit_blocks.size());
+    }
     SeqState st;
     for (size_t i = 0; i < hit_blocks.size(); ++i) {
       take(hit_blocks[i]);
@@ -351,7 +355,7 @@ void register_block_manager(py::module_& m) {
       .def("blocks_needed", &BlockManager::blocks_needed)
       .def("peek_cached", &BlockManager::peek_cached)
       .def("allocate", &BlockManager::allocate, py::arg("seq_id"), py::arg("tokens"),
-           py::arg("reserve_tokens") = 0)
+           py::arg("reserve_tokens") = 0, py::arg("use_prefix") = true)
       .def("ensure", &BlockManager::ensure)
       .def("commit", &BlockManager::commit)
       .def("free", &BlockManager::free)

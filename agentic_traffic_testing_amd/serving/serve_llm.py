@@ -3,12 +3,15 @@
 API-compatible with the reference's aiohttp front end over vLLM (llm/serve_llm.py):
 
 * ``POST /chat | /completion | /generate`` with ``{prompt|input, max_tokens?, request_id?,
-  system_prompt?, skip_chat_template?, logprobs?, presence_penalty?, frequency_penalty?,
+  system_prompt?, skip_chat_template?, logprobs?, prompt_logprobs?, presence_penalty?,
+  frequency_penalty?,
   repetition_penalty?, logit_bias?, guided_regex? | guided_choice? | guided_json?}`` ->
   ``{"output", "meta": {request_id,
   latency_ms, queue_wait_s, prompt_tokens, completion_tokens, total_tokens, otel}}`` (with an
   integer ``logprobs`` also ``"logprobs": {tokens, token_ids, token_logprobs,
-  top_logprobs}``, one entry per generated token); 400 on bad JSON /
+  top_logprobs}``, one entry per generated token; with an integer ``prompt_logprobs`` also
+  ``"prompt_logprobs"``, the same four lists with one entry per prompt token after chat
+  template and truncation, the first token's logprob null); 400 on bad JSON /
   missing prompt, 503 before init, 500 ``Generation failed: ...`` (serve_llm.py:731-942);
 * ``GET /health | /ready | /live`` -> ``{"status": "ok"}``; ``GET /metrics`` -> Prometheus
   text of the exact ``llm_*`` families (serving/metrics.py);
@@ -223,6 +226,18 @@ async def handle_chat(request: web.Request) -> web.Response:
             except ValueError as exc:
                 _leave()
                 return web.json_response({"error": str(exc)}, status=400)
+        # optional integer "prompt_logprobs" (SamplingParams.prompt_logprobs: 0 = each prompt
+        # token's logprob, N <= 20 = also each position's N most likely tokens); absent: the
+        # response is unchanged.  A bad value, or an engine that cannot serve it (tensor
+        # parallel), is a 400 with the engine's own message
+        want_plp = data.get("prompt_logprobs")
+        if want_plp is not None:
+            try:
+                check = getattr(st.engine, "check_sampling", None)
+                (check or SamplingParams.check)(SamplingParams(prompt_logprobs=want_plp))
+            except ValueError as exc:
+                _leave()
+                return web.json_response({"error": str(exc)}, status=400)
         # optional penalties and "logit_bias" (a JSON object: its keys are strings holding token
         # ids); absent: nothing changes.  A bad value, or an engine that cannot serve them
         # (tensor parallel), is a 400 with the engine's own message
@@ -289,7 +304,8 @@ async def handle_chat(request: web.Request) -> web.Response:
 
         sp = SamplingParams(temperature=float(data.get("temperature", st.s.temperature)),
                             max_tokens=max(1, eff_new), ignore_eos=bool(data.get("ignore_eos", st.s.ignore_eos)),
-                            seed=data.get("seed"), logprobs=want_lp, **pen_kw, **guide_kw)
+                            seed=data.get("seed"), logprobs=want_lp, prompt_logprobs=want_plp,
+                            **pen_kw, **guide_kw)
         queue_wait = 0.0
         final = None
         try:
@@ -390,6 +406,8 @@ async def handle_chat(request: web.Request) -> web.Response:
         body = {"output": text, "meta": meta}
         if want_lp is not None:
             body["logprobs"] = _logprobs_body(st, final)
+        if want_plp is not None:
+            body["prompt_logprobs"] = _prompt_logprobs_body(st, ids, final)
         return web.json_response(body)
 
 
@@ -429,6 +447,26 @@ def _logprobs_body(st: ServerState, final) -> dict:
         "token_logprobs": lps,
         "top_logprobs": [[{"token": st.tok.decode([i]), "token_id": i, "logprob": v}
                           for i, v in alts] for alts in tops],
+    }
+
+
+def _prompt_logprobs_body(st: ServerState, ids: list, final) -> dict:
+    """The "prompt_logprobs" object of a /chat response: four lists, one entry per prompt token
+    as the engine saw the prompt (after chat template and truncation) - its text, id, logprob
+    given the tokens before it and the position's alternatives; the first token has nothing
+    before it: its logprob and alternatives are null."""
+    ids = list(ids)
+    lps = list(final.prompt_logprobs or []) if final is not None else []
+    tops = list(final.prompt_top_logprobs or []) if final is not None else []
+    lps += [None] * (len(ids) - len(lps))
+    tops += [None] * (len(ids) - len(tops))
+    return {
+        "tokens": [st.tok.decode([t]) for t in ids],
+        "token_ids": ids,
+        "token_logprobs": lps[:len(ids)],
+        "top_logprobs": [None if alts is None else
+                         [{"token": st.tok.decode([i]), "token_id": i, "logprob": v}
+                          for i, v in alts] for alts in tops[:len(ids)]],
     }
 
 

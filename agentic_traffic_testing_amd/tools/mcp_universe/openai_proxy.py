@@ -19,6 +19,9 @@ Same contract as reference tools/mcp_universe/openai_proxy.py:43-165:
   forwarded as ``guided_json: S``; ``{"type": "text"}``, ``{"type": "json_object"}`` (recursive
   JSON is not a regular language: out of scope) and requests without these keys are forwarded
   exactly as before;
+* vLLM's integer ``prompt_logprobs`` is forwarded as sent when present and the backend's
+  ``prompt_logprobs`` object comes back under the same top-level key of the reply; requests
+  without it are forwarded exactly as before;
 * ``GET /health`` and ``/ready`` report the backend URL; default port 8110.
 
 Deliberate fix (SURVEY §2.1 T5 notes the reference always returns null usage): when the
@@ -136,7 +139,8 @@ async def handle_chat_completions(request: web.Request) -> web.Response:
         body["logprobs"] = k if isinstance(k, int) and not isinstance(k, bool) and k > 0 else 0
     # OpenAI's penalties and logit_bias (and vLLM's repetition_penalty extension) go to the
     # backend as sent - it validates them and answers 400; absent keys add nothing
-    for key in PENALTY_KEYS + GUIDE_KEYS:
+    # (and vLLM's prompt_logprobs extension likewise)
+    for key in PENALTY_KEYS + GUIDE_KEYS + ("prompt_logprobs",):
         if payload.get(key) is not None:
             body[key] = payload[key]
     # OpenAI's structured output: the schema of a json_schema response format is the guide
@@ -163,14 +167,17 @@ async def handle_chat_completions(request: web.Request) -> web.Response:
               "finish_reason": "stop"}
     if want_lp:
         choice["logprobs"] = {"content": _logprobs_content(data)}
-    return web.json_response({
+    reply = {
         "id": f"chatcmpl-{uuid.uuid4().hex[:24]}",
         "object": "chat.completion",
         "created": int(time.time()),
         "model": payload.get("model", "local-llm"),
         "choices": [choice],
         "usage": _usage(data),
-    })
+    }
+    if payload.get("prompt_logprobs") is not None:
+        reply["prompt_logprobs"] = data.get("prompt_logprobs") if isinstance(data, dict) else None
+    return web.json_response(reply)
 
 
 def create_app(backend_url: str) -> web.Application:
