@@ -8,15 +8,20 @@ One step = one forward over a decode-first ``Batch`` (scheduler.py) followed by 
   i.e. ~1.9 M tokens for Llama-3-8B at 0.9 of 288 GB.
 * **Metadata** - the native block manager emits int32 arrays which are packed into ONE
   pinned host buffer and moved with ONE async H2D copy per step; every device metadata
-  tensor is a view into the matching device buffer.
+  tensor is a view into the matching device buffer.  What a step is beyond its arrays - the
+  layout's sizes, graph bucket, variant, scoring and verify fields - is one ``StepHeader``
+  (step_msg.py), which ``_run`` executes; its variant is decoded once into a ``SamplePlan``
+  and bound to the step's sampling fields as the ``SampleArgs`` of the model's one sampler
+  tail (``LlamaModel.sample_tail``).
 * **hipGraphs** - decode-only steps are padded to a bucket (1, 2, 4, 8, ...) and replayed
   from a captured graph that contains the whole forward, the LM head and the sampler, so a
   decode step costs one graph launch instead of ~330 kernel launches.
 * **Tensor parallelism** - rank 0 owns scheduler + block manager; every step it packs the
-  same int32 metadata it uploads into a step message (header + payload) and publishes it
-  on a shared-memory channel (runtime/csrc/shm_channel.cpp).  TP worker ranks
-  (``serve_worker``) replay exactly the same kernel / collective sequence from it, graph
-  captures included, so the RCCL all-reduces line up.
+  same int32 metadata it uploads into a step message (``StepHeader.words()`` + payload) and
+  publishes it on a shared-memory channel (runtime/csrc/shm_channel.cpp).  TP worker ranks
+  (``serve_worker``) parse each message back into a ``StepHeader`` and replay exactly the
+  same kernel / collective sequence from it, graph captures (OP_CAPTURE) included, so the
+  RCCL all-reduces line up.
 """
 from __future__ import annotations
 
@@ -31,10 +36,13 @@ import torch
 
 from .. import ops
 from ..config import EngineConfig, ModelConfig
-from ..models.llama import AttnMeta, LlamaModel, torch_dtype
+from ..models.llama import AttnMeta, LlamaModel, SampleArgs, torch_dtype
 from ..ops import reference as ref
 from ..runtime import BlockManager
 from .scheduler import Batch
+from .step_msg import (HDR_WORDS, LP_NONE, LP_SAMPLED, LP_TOPN, OP_BARRIER, OP_CAPTURE, OP_STEP,
+                       OP_STOP, SCORE_TOPN, TOP_N, V_GUIDE, V_PENALTY, V_SCORE, V_TOPKP,
+                       SamplePlan, StepHeader, sample_plan, variant_code, variant_lp)
 
 
 def _even(n: int) -> int:
@@ -124,36 +132,30 @@ class MetaLayout:
                 host[o:o + n][:a.size] = a.reshape(-1)
 
 
-# step-message header (int32 words) shared by rank 0 and the TP workers
-HDR_WORDS = 12
-OP_STEP, OP_CAPTURE, OP_STOP, OP_BARRIER = 1, 2, 3, 4
+class SlotPool:
+    """Rows of a per-sequence device state ("slots"), handed to running sequences (host
+    bookkeeping only): ``slots`` maps seq_id -> slot, ``free`` holds the rest."""
 
-# step variant (header word 8, third part of a graph key, word 3 of OP_CAPTURE): bit 0 - some
-# row samples with top-k / top-p (logits materialised); bits 1-2 - the logprob mode of the
-# step's most demanding sequence; bit 3 - some sequence has a penalty or a logit bias (logits
-# materialised, penalised into an fp32 buffer before the sampler, token counts updated after);
-# bit 4 - some sequence is guided (logits materialised, masked into the fp32 buffer by its
-# automaton state before the sampler, the state advanced after); bit 5 - a prefill step some
-# of whose rows are scored for prompt logprobs (never a graph step: header word 7, a graph
-# step's bucket, then holds the number of scoring rows, plus SCORE_TOPN when some sequence
-# wants the alternatives too)
-V_TOPKP = 1
-V_PENALTY = 8
-V_GUIDE = 16
-V_SCORE = 32
-SCORE_TOPN = 1 << 30
-LP_NONE, LP_SAMPLED, LP_TOPN = 0, 1, 2   # no logprobs / the sampled token's / + the top-N
-TOP_N = ops.MAX_TOP_LOGPROBS             # a top-N step computes this many; requests cut theirs
+    def __init__(self, feature: str, n: int):
+        self.feature = feature
+        self.slots: dict[int, int] = {}
+        self.free = list(range(n - 1, -1, -1))   # slot 0 goes first
 
+    def acquire(self, seq_id: int) -> tuple[int, bool]:
+        """(the sequence's slot, whether it is fresh: the caller seeds it)."""
+        slot = self.slots.get(seq_id)
+        if slot is not None:
+            return slot, False
+        if not self.free:  # running sequences <= max_num_seqs, each holds at most one
+            raise RuntimeError(f"no free {self.feature} slot: a finished, aborted or preempted "
+                               "sequence was not released")
+        slot = self.slots[seq_id] = self.free.pop()
+        return slot, True
 
-def variant_code(topkp: bool, lp_mode: int, penalty: bool = False, guide: bool = False,
-                 score: bool = False) -> int:
-    return (int(bool(topkp)) | (lp_mode << 1) | (V_PENALTY if penalty else 0)
-            | (V_GUIDE if guide else 0) | (V_SCORE if score else 0))
-
-
-def variant_lp(variant: int) -> int:
-    return (variant >> 1) & 3
+    def release(self, seq_id: int) -> None:
+        slot = self.slots.pop(seq_id, None)
+        if slot is not None:
+            self.free.append(slot)
 
 
 class ModelRunner:
@@ -369,14 +371,15 @@ class ModelRunner:
         # sampling penalties (SamplingParams.penalised): device state allocated with the first
         # such request (ensure_penalty_state), one row ("slot") per penalised running sequence
         self.pen: dict | None = None
-        self._pen_slot: dict[int, int] = {}   # seq_id -> slot (seeded)
-        self._pen_free: list[int] = []
+        self._pen_pool = SlotPool("penalty", cfg.max_num_seqs)
+        self._pen_slot, self._pen_free = self._pen_pool.slots, self._pen_pool.free
         # guided decoding (SamplingParams.guided): device state allocated with the first such
         # request (ensure_guide_state) - the pool of automaton tables, one current state per
         # guided running sequence ("slot") - and the host's bookkeeping of both
         self.guide: dict | None = None
-        self._guide_slots: dict[int, int] = {}    # seq_id -> slot (seeded)
-        self._guide_free: list[int] = []
+        self._guide_slot_pool = SlotPool("guide", cfg.max_num_seqs)
+        self._guide_slots, self._guide_free = (self._guide_slot_pool.slots,
+                                               self._guide_slot_pool.free)
         # guides with a range of pool rows, by Guide.key, least recently used first:
         # {"guide", "base", "refs" (sequences holding it), "uploaded"}
         self._guide_pool: "collections.OrderedDict[tuple, dict]" = collections.OrderedDict()
@@ -436,24 +439,18 @@ class ModelRunner:
             "bias_vals": torch.zeros(n, nb, dtype=torch.float32, device=dev),
             "logits": self._sampler_logits(),
         }
-        self._pen_free = list(range(n - 1, -1, -1))
 
     def _penalty_slot(self, seq) -> int:
         """The slot of a penalised sequence whose next token this step samples; a sequence
         without one (just admitted, or re-admitted after a preemption) gets a free slot, seeded
         on the current stream from its prompt and the tokens it has generated so far."""
-        slot = self._pen_slot.get(seq.seq_id)
-        if slot is None:
-            if not self._pen_free:  # running sequences <= max_num_seqs, each holds at most one
-                raise RuntimeError("no free penalty slot: a finished, aborted or preempted "
-                                   "sequence was not released")
-            slot = self._pen_free.pop()
+        slot, fresh = self._pen_pool.acquire(seq.seq_id)
+        if fresh:
             sp, pen = seq.sampling, self.pen
             bias = sp.logit_bias or {}
             ops.penalty_seed(pen["state"][slot], seq.prompt_ids, seq.output_ids,
                              pen["bias_ids"][slot], pen["bias_vals"][slot],
                              list(bias.keys()), [float(b) for b in bias.values()])
-            self._pen_slot[seq.seq_id] = slot
         return slot
 
     def penalty_release(self, seq_id: int) -> None:
@@ -476,9 +473,7 @@ class ModelRunner:
 
         A preempted sequence comes back through ``_penalty_slot``, which re-seeds from its prompt
         and all its outputs so far, so its counts continue across the recompute."""
-        slot = self._pen_slot.pop(seq_id, None)
-        if slot is not None:
-            self._pen_free.append(slot)
+        self._pen_pool.release(seq_id)
 
     def _sampler_logits(self) -> torch.Tensor:
         """The fp32 logits buffer the penalty and the guide kernels write and the sampler
@@ -511,7 +506,6 @@ class ModelRunner:
             "logits": self._sampler_logits(),
             "done_row": False,
         }
-        self._guide_free = list(range(n - 1, -1, -1))
 
     def guide_reserve(self, seq_id: int, guide) -> None:
         """Give ``guide`` a range of pool rows (host bookkeeping: first fit over the gaps
@@ -552,11 +546,8 @@ class ModelRunner:
         current stream with the pool row of its host shadow state - so a recomputed sequence
         continues mid-pattern.  The guide's rows are uploaded here, on the same stream, the
         first time one of its sequences needs them."""
-        slot = self._guide_slots.get(seq.seq_id)
-        if slot is None:
-            if not self._guide_free:  # running sequences <= max_num_seqs, each holds at most one
-                raise RuntimeError("no free guide slot: a finished, aborted or preempted "
-                                   "sequence was not released")
+        slot, fresh = self._guide_slot_pool.acquire(seq.seq_id)
+        if fresh:
             ent = self._guide_pool[self._guide_of[seq.seq_id]]
             g, base, dev = ent["guide"], ent["base"], self.guide
             if not dev["done_row"]:   # row 0 is the same in every guide's table
@@ -568,10 +559,8 @@ class ModelRunner:
                 rows = torch.from_numpy(np.where(t > 0, t + np.int16(base - 1), t))
                 dev["next"][base:base + g.num_states].copy_(rows)
                 ent["uploaded"] = True
-            slot = self._guide_free.pop()
             st = int(seq.guide_state)
             ops.guide_seed(dev["state"], slot, st + base - 1 if st > 0 else 0)
-            self._guide_slots[seq.seq_id] = slot
         return slot
 
     def guide_release(self, seq_id: int, keep_guide: bool = False) -> None:
@@ -595,9 +584,7 @@ class ModelRunner:
 
         A preempted sequence comes back through ``_guide_slot``, which seeds its slot from the
         host shadow state (``Sequence.guide_state``, advanced with every appended token)."""
-        slot = self._guide_slots.pop(seq_id, None)
-        if slot is not None:
-            self._guide_free.append(slot)
+        self._guide_slot_pool.release(seq_id)
         if not keep_guide:
             key = self._guide_of.pop(seq_id, None)
             if key is not None:
@@ -800,11 +787,21 @@ class ModelRunner:
         need = max(1, math.ceil(max_kv / pt))
         return next((p for p in buckets if p >= need), top)
 
-    def _lp_fusable(self, variant: int) -> bool:
-        """Does this variant's logprob come out of the fused LM head + sampler (the SAMPLE_LP
-        epilogue)?  The sampled token's alone, no top-k / top-p row, one GPU; every other
-        logprob variant materialises the logits for ``ops.token_logprobs``."""
-        return variant == variant_code(False, LP_SAMPLED) and self.tp_size == 1
+    def _sample_args(self, v: dict, variant: int = 0) -> SampleArgs:
+        """A step's sampling fields bound to its decoded variant (``sample_plan``)."""
+        plan = sample_plan(variant, self.tp_size)
+        # penalty variant: the materialised logits go through ops.penalty_apply into the fp32
+        # buffer, the sampler reads that, ops.penalty_update counts its tokens (logprobs stay
+        # on the raw logits)
+        pen = None
+        if plan.penalty:
+            pen = {**self.pen, "slot": v["pen_slot"], "rep": v["pen_rep"],
+                   "freq": v["pen_freq"], "pres": v["pen_pres"]}
+        # guide variant: ops.guide_apply masks the (penalised) logits by each row's automaton
+        # state, ops.guide_advance moves the state by the sampled token
+        gd = {**self.guide, "slot": v["guide_slot"]} if plan.guide else None
+        return SampleArgs(v["temperature"], v["seeds"], v["steps"],
+                          v["top_p"] if plan.topkp else None, v["top_k"], plan, pen, gd)
 
     def _forward_sample(self, v: dict, md: AttnMeta, num_parts: int, variant: int = 0,
                         score_top: int = 0):
@@ -819,39 +816,16 @@ class ModelRunner:
         rows see exactly what they see without it."""
         m = self.model
         T = v["input_ids"].shape[0]
-        special = bool(variant & V_TOPKP)
-        lp_mode = variant_lp(variant)
-        lp_fused = self._lp_fusable(variant)
-        # penalty variant: the materialised logits go through ops.penalty_apply into the fp32
-        # buffer, the sampler reads that, ops.penalty_update counts its tokens (logprobs stay
-        # on the raw logits)
-        pen = None
-        if variant & V_PENALTY:
-            pen = {**self.pen, "slot": v["pen_slot"], "rep": v["pen_rep"],
-                   "freq": v["pen_freq"], "pres": v["pen_pres"]}
-        # guide variant: ops.guide_apply masks the (penalised) logits by each row's automaton
-        # state, ops.guide_advance moves the state by the sampled token
-        gd = None
-        if variant & V_GUIDE:
-            gd = {**self.guide, "slot": v["guide_slot"]}
-        # logits are materialised for top-k / top-p, penalties, guides and for every logprob
-        # the fused sampler cannot record
-        mat = (special or pen is not None or gd is not None
-               or (lp_mode != LP_NONE and not lp_fused))
-        # alternatives a materialised logprob step computes (None: no logprobs)
-        lp_top = None if lp_mode == LP_NONE else (TOP_N if lp_mode == LP_TOPN else 0)
-        score = bool(variant & V_SCORE)
+        args = self._sample_args(v, variant)
+        score = args.plan.score
         if (self.fused_decode and md.num_tiles == 0 and not score
                 and md.num_decode == T and m.decode_step_fusable(T)):
             ws = self._ws_for(T)
             # grid over this step's partition bucket only (num_parts covers every row, in
             # the partition size of this batch size: parts_bucket)
             ws = {**ws, "max_parts": min(num_parts, ws["max_parts"])}
-            return m.forward_decode(v["input_ids"], md, self.k_layers, self.v_layers,
-                                    ws, v["temperature"], v["seeds"], v["steps"],
-                                    prev_tokens=self.ws["tokens"], feed_prev=v["feed_prev"],
-                                    top_p=v["top_p"] if special else None, top_k=v["top_k"],
-                                    lp_top=lp_top, lp_fused=lp_fused, penalty=pen, guide=gd)
+            return m.forward_decode(v["input_ids"], md, self.k_layers, self.v_layers, ws, args,
+                                    prev_tokens=self.ws["tokens"], feed_prev=v["feed_prev"])
         decode_only = md.num_tiles == 0 and md.num_decode == T
         # final norm on the sampled rows only (each sequence's last token)
         last = m.forward(v["input_ids"], md, self.k_layers, self.v_layers, self.part_out,
@@ -860,36 +834,19 @@ class ModelRunner:
                          feed_prev=v["feed_prev"] if decode_only else None,
                          rows=(torch.cat([v["logits_idx"], v["score_idx"]]) if score
                                else v["logits_idx"]))
-        if score:
-            # one gather and one final norm for both kinds of row: the first rows go to the
-            # sampler as ever, the rest are scored
-            n_s = v["logits_idx"].shape[0]
-            last, scored = last[:n_s], last[n_s:]
-            toks = self._sample_last(last, v, mat, special, pen, gd, lp_top, lp_fused,
-                                     decode_only)
-            self._score_dev = m.score_rows(scored, v["score_tgt"], score_top,
-                                           self.score_ws or None, fused=self.score_fused)
-            return toks
-        return self._sample_last(last, v, mat, special, pen, gd, lp_top, lp_fused, decode_only)
-
-    def _sample_last(self, last, v: dict, mat: bool, special: bool, pen, gd, lp_top, lp_fused,
-                     decode_only: bool):
-        """The sampler over a step's normalised last-token rows (``_forward_sample``)."""
-        m = self.model
-        if not mat and m.sampler_fusable(last.shape[0]) and last.shape[0] <= self.max_seqs:
-            # fused LM head + Gumbel-max sampler on the (already normalised) last rows
-            return m.sample_rows(last, 0.0, v["temperature"], v["seeds"], v["steps"], self.ws,
-                                 logprobs=lp_fused)
-        logits = m.compute_logits(last)
+        # one gather and one final norm for both kinds of row: the first rows go to the
+        # sampler as ever, the rest are scored
+        n = v["logits_idx"].shape[0]
+        last, scored = last[:n], last[n:]
         # decode-only steps sample straight into ws["tokens"]: a graph replay (and the next
         # look-ahead step's embed) reads the samples from there, so the captured sampler must
         # write them there too (a fresh tensor would leave the previous step's tokens behind)
-        out = self.ws["tokens"][:logits.shape[0]] if decode_only else None
-        toks = m.sample_logits(logits, v["temperature"], v["seeds"], v["steps"],
-                               top_p=v["top_p"] if special else None, top_k=v["top_k"],
-                               out=out, penalty=pen, guide=gd)
-        if lp_top is not None:
-            m.logits_logprobs(logits, toks, lp_top, self.ws)
+        toks = m.sample_tail(last, 0.0, args, self.ws,
+                             out=self.ws["tokens"][:n] if decode_only else None,
+                             fused_ok=m.sampler_fusable(n) and n <= self.max_seqs)
+        if score:
+            self._score_dev = m.score_rows(scored, v["score_tgt"], score_top,
+                                           self.score_ws or None, fused=self.score_fused)
         return toks
 
     # ------------------------------------------------------------------------------------
@@ -973,11 +930,10 @@ class ModelRunner:
         self.steps += 1
         variant = self._variant(batch)
         lay, arrays = self._prepare(batch)
-        score_word = 0
+        topn = False
         if lay.score:
             variant |= V_SCORE
             topn = any(s.sampling.prompt_logprobs for s in batch.seqs if s.scoring)
-            score_word = lay.score | (SCORE_TOPN if topn else 0)
         max_kv = int(arrays["seq_kvlen"][:batch.num_decode].max()) if batch.num_decode else 0
         if batch.num_decode == n and lay.NT == 0:
             # decode-only: in the partition size of this batch size (>= the 256-token count
@@ -986,10 +942,9 @@ class ModelRunner:
         else:
             num_parts = max(1, math.ceil(max_kv / self.part_tokens))
         host = self._pack(lay, arrays)
-        hdr = np.array([OP_STEP, lay.T, lay.S, lay.W, lay.NT, batch.num_decode, num_parts,
-                        score_word, variant, n, lay.size, 0], dtype=np.int32)
-        if self.publisher is not None:
-            self.publisher.publish(np.concatenate([hdr, host]))
+        hdr = StepHeader(OP_STEP, lay.T, lay.S, lay.W, lay.NT, batch.num_decode, num_parts, 0,
+                         variant, n, lay.size, score_rows=lay.score, score_topn=topn)
+        self._publish(hdr, host)
         toks = self._run(hdr)
         if self.is_cuda and lay.T > n and self.model.prefill_gemm != "hipblaslt":
             # prefill rows ran: fetch the hand-written GEMM's error word with the tokens'
@@ -1086,10 +1041,9 @@ class ModelRunner:
         num_parts = max(1, math.ceil(int(arrays["seq_kvlen"].max()) / pt))
         if num_parts > mp:
             raise ValueError("verify(): context past verify_max_kv()")
-        host = self._pack(lay, arrays)
-        # header word 11: longest qlen | shortest qlen << 8 of a verify step (0: a plain step)
-        hdr = np.array([OP_STEP, lay.T, lay.S, lay.W, 0, S, num_parts, 0, 0, S, lay.size,
-                        int(max(batch.q_len)) | int(min(batch.q_len)) << 8], dtype=np.int32)
+        self._pack(lay, arrays)
+        hdr = StepHeader(OP_STEP, lay.T, lay.S, lay.W, 0, S, num_parts, 0, 0, S, lay.size,
+                         max_qlen=int(max(batch.q_len)), min_qlen=int(min(batch.q_len)))
         toks = self._run(hdr)[:T].cpu().numpy()
         out, row = [], 0
         for n in batch.q_len:
@@ -1108,11 +1062,10 @@ class ModelRunner:
             pt, _ = self._verify_tier(md.num_decode)
             ws = {**self.ws, "part_tokens": pt, "max_parts": num_parts}
             return m.forward_decode(v["input_ids"], md, self.k_layers, self.v_layers, ws,
-                                    v["temperature"], v["seeds"], v["steps"], max_qlen=max_qlen,
-                                    min_qlen=min_qlen)
+                                    self._sample_args(v), max_qlen=max_qlen, min_qlen=min_qlen)
         hidden = m.forward(v["input_ids"], md, self.k_layers, self.v_layers, self.part_out,
                            self.part_lse, num_parts, self.part_tokens)
-        return ops.sample(m.compute_logits(hidden), v["temperature"], v["seeds"], v["steps"])
+        return m.sample_tail(hidden, 0.0, self._sample_args(v), self.ws, fused_ok=False)
 
     def take_kernel_error(self) -> int:
         """Error words seen since the previous call (the /health check), then cleared."""
@@ -1153,10 +1106,9 @@ class ModelRunner:
             num_parts = self.parts_bucket(int(arrays["seq_kvlen"][:n].max()), n)
         arrays["feed_prev"] = np.array([1 if lookahead else 0], dtype=np.int32)
         host = self._pack(lay, arrays)
-        hdr = np.array([OP_STEP, lay.T, lay.S, lay.W, lay.NT, batch.num_decode, num_parts,
-                        bucket, variant, n, lay.size, 0], dtype=np.int32)
-        if self.publisher is not None:
-            self.publisher.publish(np.concatenate([hdr, host]))
+        hdr = StepHeader(OP_STEP, lay.T, lay.S, lay.W, lay.NT, batch.num_decode, num_parts,
+                         bucket, variant, n, lay.size)
+        self._publish(hdr, host)
         t1 = time.perf_counter()
         self._run(hdr)
         dev_toks = self.ws["tokens"]  # _run leaves decode samples here (graph or eager)
@@ -1203,35 +1155,38 @@ class ModelRunner:
         ids = host[R:R + R * TOP_N].view(np.int32).reshape(R, TOP_N)[:n].copy()
         return lp, ids, host[R + R * TOP_N:].reshape(R, TOP_N)[:n].copy()
 
-    def _run(self, hdr):
+    def _publish(self, hdr: StepHeader, payload: np.ndarray | None = None) -> None:
+        """Rank 0 of a TP group: send the workers a message (a step's with its metadata)."""
+        if self.publisher is not None:
+            w = hdr.words()
+            self.publisher.publish(w if payload is None else np.concatenate([w, payload]))
+
+    def _run(self, hdr: StepHeader):
         """Execute one step from its header; the packed metadata is in ``meta_host``."""
-        T, S, W, NT, num_decode, num_parts, bucket, variant, n, size = (int(x) for x in hdr[1:11])
-        if int(hdr[11]):  # verify step: row-sized sampling fields, multi-query attention
-            lay = MetaLayout(T, S, W, NT, T)
+        T, NT, num_decode, size = hdr.T, hdr.NT, hdr.num_decode, hdr.size
+        if hdr.max_qlen:  # verify step: row-sized sampling fields, multi-query attention
+            lay = MetaLayout(T, hdr.S, hdr.W, NT, T)
             dev = self.meta_dev[:size]
             self._h2d(dev, size)
             v = lay.views(dev)
-            return self._forward_verify(v, self._meta(v, num_decode, NT), num_parts,
-                                        int(hdr[11]) & 0xFF, int(hdr[11]) >> 8)
-        n_score = score_top = 0
-        if variant & V_SCORE:  # never a graph step: word 7 is the scoring row count
-            n_score, score_top = bucket & (SCORE_TOPN - 1), (TOP_N if bucket & SCORE_TOPN else 0)
-            bucket = 0
-        if bucket:
-            key = (bucket, num_parts, variant)
+            return self._forward_verify(v, self._meta(v, num_decode, NT), hdr.num_parts,
+                                        hdr.max_qlen, hdr.min_qlen)
+        if hdr.bucket:
+            key = (hdr.bucket, hdr.num_parts, hdr.variant)
             io = self.graph_io[key]
             self._h2d(io["dev"], size)
             self.graphs[key].replay()
             self.graph_steps += 1
             return io["out"]
-        lay = MetaLayout(T, S, W, NT, penalty=bool(variant & V_PENALTY),
-                         guide=bool(variant & V_GUIDE), score=n_score)
+        lay = MetaLayout(T, hdr.S, hdr.W, NT, penalty=bool(hdr.variant & V_PENALTY),
+                         guide=bool(hdr.variant & V_GUIDE), score=hdr.score_rows)
         dev = self.meta_dev[:size]
         self._h2d(dev, size)
         v = lay.views(dev)
         md = self._meta(v, num_decode, NT)
         # every rank samples (deterministic kernels over all-gathered logits under TP)
-        out = self._forward_sample(v, md, num_parts, variant, score_top)
+        out = self._forward_sample(v, md, hdr.num_parts, hdr.variant,
+                                   TOP_N if hdr.score_topn else 0)
         if NT == 0 and num_decode == T and out is not None:
             # every rank keeps the decode samples where a look-ahead step embeds them from
             dev_toks = self.ws["tokens"]
@@ -1258,19 +1213,18 @@ class ModelRunner:
                     raise RuntimeError(f"TP rank {reader + 1}: rank 0 died; worker exiting")
                 continue
             last, data = msg
-            hdr = data[:HDR_WORDS]
-            op = int(hdr[0])
-            if op == OP_STOP:
+            hdr = StepHeader.parse(data)
+            if hdr.op == OP_STOP:
                 return
-            if op == OP_CAPTURE:
-                self.capture(int(hdr[1]), int(hdr[2]) or None, int(hdr[3]))
+            if hdr.op == OP_CAPTURE:
+                self.capture(hdr.bucket, hdr.num_parts or None, hdr.variant)
                 continue
-            if op == OP_BARRIER:
+            if hdr.op == OP_BARRIER:
                 if self.is_cuda:
                     torch.cuda.synchronize(self.device)
                 self.comm.barrier()
                 continue
-            size = int(hdr[10])
+            size = hdr.size
             # alternate pinned buffers: no stream sync per step, only an event wait on the
             # copy two steps back before its buffer is rewritten
             self._next_meta_host()[:size] = data[HDR_WORDS:HDR_WORDS + size]
@@ -1281,19 +1235,14 @@ class ModelRunner:
         """Synchronise every TP rank (device work drained, then a process-group barrier)."""
         if self.is_cuda:
             torch.cuda.synchronize(self.device)
-        if self.publisher is not None:
-            hdr = np.zeros(HDR_WORDS, dtype=np.int32)
-            hdr[0] = OP_BARRIER
-            self.publisher.publish(hdr)
+        self._publish(StepHeader(OP_BARRIER))
         if self.comm is not None:
             self.comm.barrier()
 
     def stop_workers(self):
         if self.publisher is not None:
-            hdr = np.zeros(HDR_WORDS, dtype=np.int32)
-            hdr[0] = OP_STOP
             try:
-                self.publisher.publish(hdr, 30.0)
+                self.publisher.publish(StepHeader(OP_STOP).words(), 30.0)
             finally:
                 self.publisher.close()
 
@@ -1306,10 +1255,7 @@ class ModelRunner:
         Variants other than 0 are captured on first use."""
         variant = int(variant)
         parts = parts or self._tier(bucket)[1]
-        if self.publisher is not None:
-            hdr = np.zeros(HDR_WORDS, dtype=np.int32)
-            hdr[0], hdr[1], hdr[2], hdr[3] = OP_CAPTURE, bucket, parts, variant
-            self.publisher.publish(hdr)
+        self._publish(StepHeader(OP_CAPTURE, bucket=bucket, num_parts=parts, variant=variant))
         penalty = bool(variant & V_PENALTY)
         if penalty:
             self.ensure_penalty_state()  # (allocated with the request: a no-op here)
@@ -1452,5 +1398,6 @@ class ModelRunner:
 
 
 __all__ = ["ModelRunner", "MetaLayout", "ref", "HDR_WORDS", "OP_STEP", "OP_CAPTURE", "OP_STOP",
-           "OP_BARRIER", "LP_NONE", "LP_SAMPLED", "LP_TOPN", "TOP_N", "V_PENALTY", "V_GUIDE",
-           "variant_code", "variant_lp"]
+           "OP_BARRIER", "LP_NONE", "LP_SAMPLED", "LP_TOPN", "TOP_N", "V_TOPKP", "V_PENALTY",
+           "V_GUIDE", "V_SCORE", "SCORE_TOPN", "StepHeader", "SamplePlan", "sample_plan",
+           "SlotPool", "variant_code", "variant_lp"]

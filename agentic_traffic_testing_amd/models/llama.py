@@ -60,6 +60,20 @@ class AttnMeta:
 
 
 @dataclass
+class SampleArgs:
+    """What one step's sampler tail (``LlamaModel.sample_tail``) takes: the per-row device
+    tensors, the decoded step variant and the penalty / guide state bound to this step."""
+    temperature: torch.Tensor
+    seeds: torch.Tensor
+    steps: torch.Tensor
+    top_p: torch.Tensor | None    # None unless plan.topkp
+    top_k: torch.Tensor
+    plan: object                  # SamplePlan (engine/step_msg.py)
+    penalty: dict | None = None   # the runner's penalty state + "slot" / "rep" / "freq" / "pres"
+    guide: dict | None = None     # the runner's guide state + "slot"
+
+
+@dataclass
 class LayerWeights:
     input_norm: torch.Tensor
     qkv: torch.Tensor | None
@@ -692,35 +706,21 @@ class LlamaModel:
                 and ops.fused_kernel(rows, lm_ps, False, "sample") is not None)
 
     def forward_decode(self, input_ids: torch.Tensor, md: AttnMeta, k_caches, v_caches, ws: dict,
-                       temperature, seeds, steps, prev_tokens=None,
-                       feed_prev=None, top_p=None, top_k=None, max_qlen: int = 1,
-                       min_qlen: int = 1, lp_top: int | None = None,
-                       lp_fused: bool = False, penalty: dict | None = None,
-                       guide: dict | None = None) -> torch.Tensor:
+                       args: SampleArgs, prev_tokens=None, feed_prev=None, max_qlen: int = 1,
+                       min_qlen: int = 1) -> torch.Tensor:
         """Fused decode step; returns sampled ids, one per row.  Every sequence has one query
         row - or, in a verify step of speculative decoding (``max_qlen`` > 1: the longest of
         the batch), sequence s of ``md.num_decode`` has the rows ``md.seq_qstart[s]`` ..
         ``md.seq_qstart[s + 1] - 1`` (its pending token and its drafts, at most 16 // G), the
         attention is ``ops.attention_decode_mq`` (the multi-query kernel for the sequences with
         drafts, the one-token kernel for those without; ``min_qlen``: the shortest qlen) and
-        ``temperature`` / ``seeds`` / ``steps`` are per row.
+        ``args``' temperature / seeds / steps are per row.
 
         Per layer: [RMSNorm+QKV+RoPE+KV-write] -> [paged attention, in-kernel split-K
         combine] -> [o_proj + residual add] -> [RMSNorm+gate_up+SiLU*up] ->
-        [down_proj + residual add]; then [final RMSNorm + LM head + sampler].  5 kernels per
-        layer instead of ~10, no normalised activations or logits ever hit HBM.  With
-        ``top_p`` / ``top_k`` (per-row device tensors) the step ends in final RMSNorm + LM head
-        + the top-k / top-p sampler kernel instead (logits materialised).
-
-        ``lp_top`` (None: off): the step also leaves each row's sampled-token logprob in
-        ws["lp"] - with ``lp_fused`` from the fused LM head + sampler's logprob epilogue (same
-        launch count, tokens bit-identical to the plain step's), else from the materialised
-        logits through ``ops.token_logprobs`` with its ``lp_top`` alternatives in
-        ws["top_ids"] / ws["top_lp"].
-
-        ``penalty`` / ``guide`` (see ``sample_logits``): the logits are materialised as for
-        top-k / top-p and sampled through the penalty / guide tail; logprobs still read the raw
-        logits."""
+        [down_proj + residual add]; then ``sample_tail``: [final RMSNorm + LM head + sampler].
+        5 kernels per layer instead of ~10, no normalised activations or logits ever hit HBM -
+        unless ``args.plan`` materialises the logits."""
         eps = self.cfg.rms_norm_eps
         nq, nkv = self.n_heads, self.n_kv_heads
         B = input_ids.shape[0]
@@ -754,17 +754,34 @@ class LlamaModel:
             ops.decode_gate_up_silu(residual, eps=eps, out=act,
                                     **self._decode_w(L, "gate_up", B))
             self._row_parallel(act, L, "down", residual)
-        if top_p is not None or penalty is not None or guide is not None or \
-                (lp_top is not None and not lp_fused):
-            logits = self.compute_logits(ops.rms_norm(residual, self.norm, eps))
-            toks = self.sample_logits(logits, temperature, seeds, steps, top_p=top_p,
-                                      top_k=top_k, out=ws["tokens"][:B], penalty=penalty,
-                                      guide=guide)
-            if lp_top is not None:
-                self.logits_logprobs(logits, toks, lp_top, ws)
-            return toks
-        return self.sample_rows(residual, eps, temperature, seeds, steps, ws,
-                                logprobs=lp_top is not None)
+        return self.sample_tail(residual, eps, args, ws, out=ws["tokens"][:B], fused_ok=True)
+
+    def sample_tail(self, x: torch.Tensor, eps: float, args: SampleArgs, ws: dict, out=None,
+                    fused_ok: bool = True) -> torch.Tensor:
+        """The end of every step: one token per row of ``x`` (``eps`` > 0: rows still to be
+        normalised; 0: already normalised, as ``forward`` returns them).
+
+        Fused (the plan materialises nothing and ``fused_ok``: ``sampler_fusable`` rows):
+        ``sample_rows``, the LM head and the sampler in one kernel, tokens in ws["tokens"];
+        with ``plan.lp_fused`` its logprob epilogue leaves each sampled token's logprob in
+        ws["lp"] (same launch count, tokens bit-identical to the plain step's).
+
+        Materialised (top-k / top-p, penalties, guides, every other logprob mode, or rows the
+        fused kernels do not take): [RMSNorm] -> ``compute_logits`` -> ``sample_logits`` into
+        ``out`` (None: a fresh tensor) -> with ``plan.lp_top`` ``ops.token_logprobs`` of the
+        samples and their ``lp_top`` alternatives into ws["lp"] / ws["top_ids"] / ws["top_lp"]
+        (logprobs read the raw logits, not the penalised or masked ones)."""
+        plan = args.plan
+        if not plan.materialise and fused_ok:
+            return self.sample_rows(x, eps, args.temperature, args.seeds, args.steps, ws,
+                                    logprobs=plan.lp_fused)
+        logits = self.compute_logits(ops.rms_norm(x, self.norm, eps) if eps > 0 else x)
+        toks = self.sample_logits(logits, args.temperature, args.seeds, args.steps,
+                                  top_p=args.top_p, top_k=args.top_k, out=out,
+                                  penalty=args.penalty, guide=args.guide)
+        if plan.lp_top is not None:
+            self.logits_logprobs(logits, toks, plan.lp_top, ws)
+        return toks
 
     @staticmethod
     def sample_logits(logits: torch.Tensor, temperature, seeds, steps, top_p=None, top_k=None,
